@@ -1,7 +1,7 @@
 # Convenience targets (everything is also reachable through python -m ...).
 PY ?= python3
 
-.PHONY: build native canary test test-gpu sanitize analyze bench suite soak probes inspect run-fixture image clean
+.PHONY: build native canary test test-gpu sanitize analyze bench bench-full suite soak probes inspect run-fixture image clean
 
 build:            ## C++ core (pybind11 .so) + gfx950 HIP canary, in-tree
 	$(PY) -m k8s_gpu_device_plugin_amd._build
@@ -19,8 +19,10 @@ sanitize:         ## native self-test, then the integration tests, under ASan+UB
 	$(PY) -m pytest tests/test_sanitized_suite.py -q
 analyze:          ## clang static analyzer over native/*.cpp (fails on any finding)
 	scripts/analyze.sh
-bench:
+bench:            ## the timed steps alone
 	$(PY) bench.py --gpus 1 --steps 20 --warmup 3
+bench-full:       ## ... plus the canary, the floors, the tail attribution and the host fingerprint
+	$(PY) bench.py --gpus 1 --steps 20 --warmup 3 --full
 suite:            ## BASELINE.json configs 1-5 + scaling + health propagation
 	$(PY) -m k8s_gpu_device_plugin_amd.benchmark.suite --json suite.json
 soak:             ## daemon under Allocate + scrapes + /restart every 250 ms for 2 min (real backend if present)

@@ -21,15 +21,22 @@ is better; kubelet is a compiled grpc-go client, and a Python client's own ~80 u
 call would hide the plugin); the grpcio-client p50/p99 are reported alongside;
 ``scrape_rps`` = all ranks' completed scrapes / the slowest rank's scrape window (the
 ranks scrape concurrently, so this is the daemon's aggregate throughput).  Before timing,
-each rank validates its GPU and its allocation: the gfx950 canary (HBM pattern + MFMA
-exactness/throughput) passes on the rank's device, in a child process that exits before
-the rank loads torch or joins the RCCL group, and the returned render node exists.  The
+each rank validates its allocation: the returned render node exists.  With ``--full`` it
+validates its GPU too: the gfx950 canary (HBM pattern + MFMA exactness/throughput) passes
+on the rank's device, in a child process that exits before the rank loads torch or joins
+the RCCL group.  The
 run fails unless WORLD_SIZE == --gpus == the number of devices the daemon advertised
 (one kubelet-client rank per advertised GPU).  Rank r allocates the device whose host HIP
 ordinals (``hip_ids`` of ``amdgpu_partition_info``, from amdsmi's enumeration info) hold
 its LOCAL_RANK (mapped through ROCR_/HIP_VISIBLE_DEVICES to the host's numbering when
 they are set), so the canary, ``torch.cuda.set_device(local_rank)`` and the allocation
 name the same GPU even where the HIP runtime's numbering differs from BDF order.
+
+A plain run sets up, warms up, times the K steps and prints the result line (the
+percentiles of the timed calls); ``--dump-outputs DIR`` also writes the answers the last
+timed step received, as ``DIR/<name>.npy``.  Everything below, the canary, the tail
+attribution from the daemon's call trace (``allocate_tail``, ``placement``), the allocator
+probe and the host fingerprint are measured only with ``--full``, after the timed steps.
 
 Speed-of-light references, measured untimed in the same run: ``uds_roundtrip_floor_p50_us``
 (the same unix-socket exchange between two threads, no protocol work, sleeping server
@@ -631,6 +638,155 @@ def start_daemon(n_gpus: int, grpc_server: str, workdir: str, profile_dir: str =
     return proc, kubelet, port, regs[0], backend
 
 
+def dump_outputs(out_dir: str, received: dict, h2, alloc_req: bytes, pref_req: bytes, rank: int, world: int) -> None:
+    """--dump-outputs: what a kubelet-side caller of the timed path received, one float32
+    array of the answer's bytes per file.  ``allocate_response`` and ``preferred_response``
+    are the last answers of the last timed step (grpcio client).  The compiled client's
+    timed loop drops its payloads, so ``*_h2`` are its answers to one more call each with
+    the same requests, made after the timed window.  The requests name the devices of a
+    fixed enumeration, so the same arguments on the same node give the same arrays.  A
+    rank of a multi-rank run adds ``_rank<r>`` to its names."""
+    import numpy as np
+
+    from k8s_gpu_device_plugin_amd.api import v1beta1
+    arrays = dict(received)
+    for name, method, req in (("allocate_response_h2", v1beta1.METHOD_ALLOCATE, alloc_req),
+                              ("preferred_response_h2", v1beta1.METHOD_GET_PREFERRED, pref_req)):
+        status, payload, _ = h2.unary(method, req)
+        if status != 0:
+            raise RuntimeError("%s: grpc-status %d" % (name, status))
+        arrays[name] = payload
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, payload in sorted(arrays.items()):
+        np.save(os.path.join(out_dir, name + suffix + ".npy"),
+                np.frombuffer(bytes(payload), dtype=np.uint8).astype(np.float32))
+
+
+def full_measurements(mine: dict, args, rank: int, workdir: str, info: dict, batches, busy_log, n, nb, h2, conn,
+                      alloc_raw, alloc_req: bytes, pref_req: bytes, body_len: int) -> None:
+    """--full: everything the run measures besides its timed steps, untimed and after
+    them, added to this rank's record ``mine``: the tail attribution and the placement
+    study from the daemon's call trace, the unix-socket and TCP floors, the cold and the
+    admission case, and on rank 0 the host fingerprint and the daemon's own histograms."""
+    from k8s_gpu_device_plugin_amd.api import v1beta1
+    perf = time.perf_counter
+    # the daemon's record of every call so far (untimed): the tail attribution matches them
+    trace = read_call_trace(os.path.join(workdir, "calltrace-%s.bin" % info["resource"].split("/")[-1]))
+    mine["alloc_tail"] = _tail_stats(batches, trace, n.RPC_ALLOCATE)
+    # where the client and the daemon's worker ran, per call, and what the host is (untimed)
+    topo_cpus = {}
+    mine["placement"] = _placement_stats(batches, trace, topo_cpus, n.RPC_ALLOCATE)
+    if args.diag_cpu_busy:
+        mine["placement"]["batch_cpu_busy"] = _busy_study(batches, trace, busy_log, n.RPC_ALLOCATE)
+    client_cpus = collections.Counter(c for b in batches for c in b[2])
+    client_cpu = client_cpus.most_common(1)[0][0] if client_cpus else os.sched_getcpu()
+    worker_cpus = collections.Counter(int(c) for c in trace["cpu"]) if trace is not None and len(trace) else {}
+    mine["client_cpus"] = dict(client_cpus.most_common(4))
+    mine["worker_cpus"] = dict(collections.Counter(worker_cpus).most_common(4))
+    # Untimed speed-of-light reference: the same send/epoll_wait/recv/send/recv exchange
+    # between two threads with no HTTP/2, HPACK or protobuf work (sizes ~ this Allocate's).
+    alloc_resp_len = len(alloc_raw(alloc_req))
+    sizes = (9 + 80 + 9 + 5 + len(alloc_req), 9 + 20 + 9 + 5 + alloc_resp_len + 9 + 16)
+    floor = nb.uds_pingpong(10000, 500, *sizes)
+    mine["uds_floor_p50"] = _pct(floor, 0.5)
+    # ... and with a server thread that polls instead of sleeping (the busy-poll window);
+    # its p99 is this machine's tail for a bare back-to-back exchange (timer ticks,
+    # interrupts and other tenants land on either thread's CPU), the floor Allocate's p99
+    # is compared against
+    spin = nb.uds_pingpong(10000, 500, *sizes, server_spin=True)
+    mine["uds_floor_spin_p50"] = _pct(spin, 0.5)
+    mine["uds_floor_spin_p99"] = _pct(spin, 0.99)
+    mine["uds_floor_spin_p999"] = _pct(spin, 0.999)
+    # ... and with the server consuming each request only after its answer (MSG_PEEK, the
+    # daemon's grpc.peekReads): the bare exchange without the client's spurious wake-up
+    mine["uds_floor_spin_peek_p50"] = _pct(nb.uds_pingpong(10000, 500, *sizes, server_spin=True, peek=True), 0.5)
+    # ... and in the timed loop's own rhythm (batches of ALLOCS back-to-back exchanges, a
+    # scrape phase apart) against a server with the plugin worker's polling policy: this
+    # host's tail for that pattern, which Allocate's p99 / p99.9 are compared against
+    bf = nb.uds_pingpong_batched(args.steps, ALLOCS, int(SCRAPE_S * 1e6), *sizes,
+                                 server_poll_us=args.busy_poll_us if args.busy_poll_us is not None else 50)
+    mine["uds_floor_batched"] = (_pct(bf, 0.5), _pct(bf, 0.99), _pct(bf, 0.999), max(bf))
+    mine["uds_floor_batched_batch_p50"] = [round(_pct(bf[i:i + ALLOCS], 0.5) * 1e6, 2) for i in range(0, len(bf), ALLOCS)]
+    # Allocate against the spin floor paired in time: batches of each alternate, so a busy
+    # moment on the shared host lands on both (the floor above runs after the timed loop)
+    mine["paired"] = paired_floor(h2, nb, v1beta1.METHOD_ALLOCATE, alloc_req, sizes)
+    # kubelet-like sparse calls: 1 ms apart, every one meets a sleeping server thread
+    mine["alloc_cold"] = h2.bench_unary(v1beta1.METHOD_ALLOCATE, alloc_req, 400, 1000)
+    # ... and the bare exchange with the same 1 ms idle gap (cold caches, idle CPU states)
+    mine["uds_floor_cold_p50"] = _pct(nb.uds_pingpong(400, 20, *sizes, gap_us=1000), 0.5)
+    # a pod admission as kubelet runs it: GetPreferredAllocation, ~200 us of kubelet
+    # bookkeeping, then Allocate of the same container (2 ms idle before each admission)
+    adm = []
+    for _ in range(200):
+        time.sleep(0.002)
+        h2.bench_unary(v1beta1.METHOD_GET_PREFERRED, pref_req, 1)
+        t_go = perf() + 200e-6
+        while perf() < t_go:
+            pass
+        adm.extend(h2.bench_unary(v1beta1.METHOD_ALLOCATE, alloc_req, 1))
+    mine["alloc_admission"] = adm
+    # /metrics: one loopback TCP exchange of a scrape's size, polling server
+    mine["tcp_scrape_floor_p50"] = _pct(nb.uds_pingpong(3000, 300, 90, body_len + 400, server_spin=True, tcp=True),
+                                        0.5)
+    mine["placement_floor"] = placement_floor(nb, client_cpu, sizes)
+    if rank == 0:
+        mine["host"] = host_fingerprint(list(mine["client_cpus"]) + list(mine["worker_cpus"]))
+        mine["host"]["core_ghz"] = round(nb.core_ghz(), 3)
+    if rank == 0:  # the daemon's own time per Allocate (decode, lookup, encode), from its histogram
+        conn.request("GET", "/metrics")
+        text = conn.getresponse().read().decode()
+        mine["server_allocate_mean_s"] = _server_mean(text, "Allocate")
+        mine["server_preferred_mean_s"] = _server_mean(text, "GetPreferredAllocation")
+        mine["server_scrape_mean_s"] = _scrape_server_mean(text)
+
+
+def full_fields(gathered, n) -> dict:
+    """--full: the result line's fields for what full_measurements and the canary added to
+    the ranks' records."""
+    can = [g["canary"] for g in gathered if g["canary"]]
+    return {
+        "allocate_tail": _merge_tail([g["alloc_tail"] for g in gathered]),
+        "uds_roundtrip_floor_spin_p99_us": round(gathered[0]["uds_floor_spin_p99"] * 1e6, 2),
+        "uds_roundtrip_floor_spin_p999_us": round(gathered[0]["uds_floor_spin_p999"] * 1e6, 2),
+        # the bare exchange timed in the same batches as Allocate (p50, p99, p99.9, max)
+        "uds_roundtrip_floor_batched_us": [round(x * 1e6, 2) for x in gathered[0]["uds_floor_batched"]],
+        # Allocate and the spin floor in alternating batches after the timed loop (rank 0)
+        "allocate_vs_spin_floor_paired": gathered[0].get("paired"),
+        # per-batch p50 of the bare exchange timed in the loop's rhythm (rank 0): a host
+        # whose batches fall into a slow mode shows it here too
+        "uds_floor_batched_batch_p50_us": gathered[0].get("uds_floor_batched_batch_p50"),
+        "preferred_allocator_8gpu_size4_p50_us": _allocator_probe(n),
+        "allocate_server_mean_us": (round(gathered[0]["server_allocate_mean_s"] * 1e6, 3)
+                                    if gathered[0].get("server_allocate_mean_s") else None),
+        "uds_roundtrip_floor_p50_us": round(gathered[0]["uds_floor_p50"] * 1e6, 2),
+        "uds_roundtrip_floor_spin_p50_us": round(gathered[0]["uds_floor_spin_p50"] * 1e6, 2),
+        "uds_roundtrip_floor_spin_peek_p50_us": round(gathered[0]["uds_floor_spin_peek_p50"] * 1e6, 2),
+        "uds_roundtrip_floor_cold_p50_us": round(gathered[0]["uds_floor_cold_p50"] * 1e6, 2),
+        "allocate_cold_p50_us": round(_pct([x for g in gathered for x in g["alloc_cold"]], 0.5) * 1e6, 2),
+        "allocate_admission_p50_us": round(_pct([x for g in gathered for x in g["alloc_admission"]], 0.5) * 1e6, 2),
+        "tcp_scrape_floor_p50_us": round(gathered[0]["tcp_scrape_floor_p50"] * 1e6, 2),
+        "preferred_server_mean_us": (round(gathered[0]["server_preferred_mean_s"] * 1e6, 3)
+                                     if gathered[0].get("server_preferred_mean_s") else None),
+        # the daemon's own time per /metrics answer (render + the sendmsg that hands it over)
+        "scrape_server_mean_us": (round(gathered[0]["server_scrape_mean_s"] * 1e6, 3)
+                                  if gathered[0].get("server_scrape_mean_s") else None),
+        # where each Allocate's client and daemon worker ran relative to each other, the
+        # bare exchange between the client's CPU and one CPU of each relation, and the host
+        "placement": {"allocate_by_relation": gathered[0].get("placement"),
+                      "client_cpus": gathered[0].get("client_cpus"), "worker_cpus": gathered[0].get("worker_cpus"),
+                      "floor_spin_by_relation": gathered[0].get("placement_floor")},
+        "host": gathered[0].get("host"),
+        "canary": ({"arch": can[0]["arch"], "hbm_read_gbps": round(min(c["read_gbps"] for c in can), 1),
+                    "hbm_write_gbps": round(min(c["write_gbps"] for c in can), 1),
+                    "mfma_bf16_tflops": round(min(c["mfma_tflops"] for c in can), 1),
+                    "lds_gemm_bf16_tflops": round(min(c["gemm_tflops"] for c in can), 1),
+                    "mfma_mxfp8_tflops": round(min(c["fp8_tflops"] for c in can), 1),
+                    "mfma_mxfp4_tflops": round(min(c["fp4_tflops"] for c in can), 1),
+                    "lds_march_kb": min(c["lds_bytes"] for c in can) // 1024} if can else None),
+    }
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -651,9 +807,18 @@ def main() -> int:
     ap.add_argument("--diag-cpu-busy", action="store_true",
                     help="diagnostics: read /proc/stat around every compiled-client Allocate batch and report how "
                          "busy the client's and the worker's CPUs and their SMT siblings were (placement study)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the gfx950 canary before timing, the "
+                         "tail attribution from the daemon's call trace, the unix-socket and TCP floors, the cold "
+                         "and admission cases, the allocator probe, the CPU placement study and the host fingerprint")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps write what the last one received (the Allocate and "
+                         "GetPreferredAllocation answers, as float32 arrays of their bytes) to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.diag_cpu_busy:  # a study of the call trace: part of the full run
+        args.full = True
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     n_gpus = args.gpus
@@ -694,7 +859,7 @@ def main() -> int:
     # rate) in a child process, before this process loads torch or initialises RCCL: each
     # rank then holds exactly one HIP runtime (torch's) when the communicator comes up.
     canary_res = None
-    if not args.no_canary and resolve_backend(n, args.backend) == "amdsmi":
+    if args.full and not args.no_canary and real:
         from k8s_gpu_device_plugin_amd.ops import canary
         canary_res = canary.run_isolated(local_rank, hbm_bytes=1 << 30, timeout=300.0, passes=3)
         if not canary_res.get("ok"):
@@ -778,11 +943,11 @@ def main() -> int:
         pn.extend(h2.bench_unary(v1beta1.METHOD_GET_PREFERRED, pref_req, PREFS))
         for _ in range(ALLOCS):
             t0 = perf()
-            alloc_raw(alloc_req)
+            received["allocate_response"] = alloc_raw(alloc_req)
             a.append(perf() - t0)
         for _ in range(PREFS):
             t0 = perf()
-            pref_raw(pref_req)
+            received["preferred_response"] = pref_raw(pref_req)
             p.append(perf() - t0)
         phase_sync()
         r = nb.http_load("127.0.0.1", info["port"], "/metrics", SCRAPE_CONNS, SCRAPE_S, 0.0)
@@ -791,6 +956,7 @@ def main() -> int:
         s.extend(r["latencies_s"])
         return r["elapsed_s"], r["bytes"] // max(1, r["ok"])
 
+    received = {}  # the grpcio client's last answers (--dump-outputs)
     busy_log = []  # --diag-cpu-busy: (/proc/stat before, after) per timed batch
     junk = ([], [], [], [], [], [])
     for _ in range(args.warmup):
@@ -805,78 +971,15 @@ def main() -> int:
         scrape_time += st
     barrier()
     elapsed = perf() - t_start
-    # the daemon's record of every call so far (untimed): the tail attribution matches them
-    trace = read_call_trace(os.path.join(workdir, "calltrace-%s.bin" % info["resource"].split("/")[-1]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, received, h2, alloc_req, pref_req, rank, world)
     mine = {"elapsed": elapsed, "scrape_time": scrape_time, "alloc": rec[0], "pref": rec[1], "scrape": rec[2],
-            "alloc_native": rec[3], "pref_native": rec[4], "alloc_tail": _tail_stats(rec[5], trace, n.RPC_ALLOCATE),
-            "canary": canary_res, "body": body_len,
+            "alloc_native": rec[3], "pref_native": rec[4], "canary": canary_res, "body": body_len,
             "device": {"rank": rank, "local_rank": local_rank, "device_id": my_id, "hip_ids": my_hips,
                        "mapped_by": mapped_by}}
-    # where the client and the daemon's worker ran, per call, and what the host is (untimed)
-    topo_cpus = {}
-    mine["placement"] = _placement_stats(rec[5], trace, topo_cpus, n.RPC_ALLOCATE)
-    if args.diag_cpu_busy:
-        mine["placement"]["batch_cpu_busy"] = _busy_study(rec[5], trace, busy_log, n.RPC_ALLOCATE)
-    client_cpus = collections.Counter(c for b in rec[5] for c in b[2])
-    client_cpu = client_cpus.most_common(1)[0][0] if client_cpus else os.sched_getcpu()
-    worker_cpus = collections.Counter(int(c) for c in trace["cpu"]) if trace is not None and len(trace) else {}
-    mine["client_cpus"] = dict(client_cpus.most_common(4))
-    mine["worker_cpus"] = dict(collections.Counter(worker_cpus).most_common(4))
-    # Untimed speed-of-light reference: the same send/epoll_wait/recv/send/recv exchange
-    # between two threads with no HTTP/2, HPACK or protobuf work (sizes ~ this Allocate's).
-    alloc_resp_len = len(alloc_raw(alloc_req))
-    sizes = (9 + 80 + 9 + 5 + len(alloc_req), 9 + 20 + 9 + 5 + alloc_resp_len + 9 + 16)
-    floor = nb.uds_pingpong(10000, 500, *sizes)
-    mine["uds_floor_p50"] = _pct(floor, 0.5)
-    # ... and with a server thread that polls instead of sleeping (the busy-poll window);
-    # its p99 is this machine's tail for a bare back-to-back exchange (timer ticks,
-    # interrupts and other tenants land on either thread's CPU), the floor Allocate's p99
-    # is compared against
-    spin = nb.uds_pingpong(10000, 500, *sizes, server_spin=True)
-    mine["uds_floor_spin_p50"] = _pct(spin, 0.5)
-    mine["uds_floor_spin_p99"] = _pct(spin, 0.99)
-    mine["uds_floor_spin_p999"] = _pct(spin, 0.999)
-    # ... and with the server consuming each request only after its answer (MSG_PEEK, the
-    # daemon's grpc.peekReads): the bare exchange without the client's spurious wake-up
-    mine["uds_floor_spin_peek_p50"] = _pct(nb.uds_pingpong(10000, 500, *sizes, server_spin=True, peek=True), 0.5)
-    # ... and in the timed loop's own rhythm (batches of ALLOCS back-to-back exchanges, a
-    # scrape phase apart) against a server with the plugin worker's polling policy: this
-    # host's tail for that pattern, which Allocate's p99 / p99.9 are compared against
-    bf = nb.uds_pingpong_batched(args.steps, ALLOCS, int(SCRAPE_S * 1e6), *sizes,
-                                 server_poll_us=args.busy_poll_us if args.busy_poll_us is not None else 50)
-    mine["uds_floor_batched"] = (_pct(bf, 0.5), _pct(bf, 0.99), _pct(bf, 0.999), max(bf))
-    mine["uds_floor_batched_batch_p50"] = [round(_pct(bf[i:i + ALLOCS], 0.5) * 1e6, 2) for i in range(0, len(bf), ALLOCS)]
-    # Allocate against the spin floor paired in time: batches of each alternate, so a busy
-    # moment on the shared host lands on both (the floor above runs after the timed loop)
-    mine["paired"] = paired_floor(h2, nb, v1beta1.METHOD_ALLOCATE, alloc_req, sizes)
-    # kubelet-like sparse calls: 1 ms apart, every one meets a sleeping server thread
-    mine["alloc_cold"] = h2.bench_unary(v1beta1.METHOD_ALLOCATE, alloc_req, 400, 1000)
-    # ... and the bare exchange with the same 1 ms idle gap (cold caches, idle CPU states)
-    mine["uds_floor_cold_p50"] = _pct(nb.uds_pingpong(400, 20, *sizes, gap_us=1000), 0.5)
-    # a pod admission as kubelet runs it: GetPreferredAllocation, ~200 us of kubelet
-    # bookkeeping, then Allocate of the same container (2 ms idle before each admission)
-    adm = []
-    for _ in range(200):
-        time.sleep(0.002)
-        h2.bench_unary(v1beta1.METHOD_GET_PREFERRED, pref_req, 1)
-        t_go = perf() + 200e-6
-        while perf() < t_go:
-            pass
-        adm.extend(h2.bench_unary(v1beta1.METHOD_ALLOCATE, alloc_req, 1))
-    mine["alloc_admission"] = adm
-    # /metrics: one loopback TCP exchange of a scrape's size, polling server
-    mine["tcp_scrape_floor_p50"] = _pct(nb.uds_pingpong(3000, 300, 90, body_len + 400, server_spin=True, tcp=True),
-                                        0.5)
-    mine["placement_floor"] = placement_floor(nb, client_cpu, sizes)
-    if rank == 0:
-        mine["host"] = host_fingerprint(list(mine["client_cpus"]) + list(mine["worker_cpus"]))
-        mine["host"]["core_ghz"] = round(nb.core_ghz(), 3)
-    if rank == 0:  # the daemon's own time per Allocate (decode, lookup, encode), from its histogram
-        conn.request("GET", "/metrics")
-        text = conn.getresponse().read().decode()
-        mine["server_allocate_mean_s"] = _server_mean(text, "Allocate")
-        mine["server_preferred_mean_s"] = _server_mean(text, "GetPreferredAllocation")
-        mine["server_scrape_mean_s"] = _scrape_server_mean(text)
+    if args.full:
+        full_measurements(mine, args, rank, workdir, info, rec[5], busy_log, n, nb, h2, conn, alloc_raw, alloc_req,
+                          pref_req, body_len)
     if world > 1:
         gathered = [None] * world
         dist.all_gather_object(gathered, mine)
@@ -893,13 +996,12 @@ def main() -> int:
         scrape_t = max(g["scrape_time"] for g in gathered)
         p50 = _pct(allocs_native, 0.5) * 1e6
         p50_grpcio = _pct(allocs, 0.5) * 1e6
-        can = [g["canary"] for g in gathered if g["canary"]]
         out = {
             "metric": METRIC, "value": round(p50, 2), "unit": "us (Allocate p50, compiled h2 client; lower is better)",
             "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(t_max / args.steps * 1e3, 3), "higher_is_better": False, "scaling": "weak",
             # a control-plane workload: no tensor arithmetic on the timed path (the gfx950
-            # canary's bf16/MX-fp8/fp4 checks run untimed, see "canary")
+            # canary's bf16/MX-fp8/fp4 checks run untimed with --full, see "canary")
             "vs_baseline": None, "dtype": "n/a",
             "data": "synthetic kubelet allocation workload (%d Allocate + %d GetPreferredAllocation per client "
                     "per rank per step, %d ms of /metrics scraping on %d connections per rank per step) against "
@@ -911,59 +1013,24 @@ def main() -> int:
             "allocate_p50_us": round(p50, 2), "allocate_p99_us": round(_pct(allocs_native, 0.99) * 1e6, 2),
             "allocate_p999_us": round(_pct(allocs_native, 0.999) * 1e6, 2),
             "allocate_max_us": round(max(allocs_native) * 1e6, 2),
-            "allocate_tail": _merge_tail([g["alloc_tail"] for g in gathered]),
-            "uds_roundtrip_floor_spin_p99_us": round(gathered[0]["uds_floor_spin_p99"] * 1e6, 2),
-            "uds_roundtrip_floor_spin_p999_us": round(gathered[0]["uds_floor_spin_p999"] * 1e6, 2),
-            # the bare exchange timed in the same batches as Allocate (p50, p99, p99.9, max)
-            "uds_roundtrip_floor_batched_us": [round(x * 1e6, 2) for x in gathered[0]["uds_floor_batched"]],
-            # Allocate and the spin floor in alternating batches after the timed loop (rank 0)
-            "allocate_vs_spin_floor_paired": gathered[0].get("paired"),
-            # per-batch p50 of the bare exchange timed in the loop's rhythm (rank 0): a host
-            # whose batches fall into a slow mode shows it here too
-            "uds_floor_batched_batch_p50_us": gathered[0].get("uds_floor_batched_batch_p50"),
-            "preferred_allocator_8gpu_size4_p50_us": _allocator_probe(n),
-            "allocate_server_mean_us": (round(gathered[0]["server_allocate_mean_s"] * 1e6, 3)
-                                        if gathered[0].get("server_allocate_mean_s") else None),
             "advertised_devices": len(ids), "world_size": world,
             "rank_devices": [g["device"] for g in gathered],
             "dist_backend": (dist.get_backend() if world > 1 else None),
-            "uds_roundtrip_floor_p50_us": round(gathered[0]["uds_floor_p50"] * 1e6, 2),
-            "uds_roundtrip_floor_spin_p50_us": round(gathered[0]["uds_floor_spin_p50"] * 1e6, 2),
-            "uds_roundtrip_floor_spin_peek_p50_us": round(gathered[0]["uds_floor_spin_peek_p50"] * 1e6, 2),
-            "uds_roundtrip_floor_cold_p50_us": round(gathered[0]["uds_floor_cold_p50"] * 1e6, 2),
-            "allocate_cold_p50_us": round(_pct([x for g in gathered for x in g["alloc_cold"]], 0.5) * 1e6, 2),
-            "allocate_admission_p50_us": round(_pct([x for g in gathered for x in g["alloc_admission"]], 0.5) * 1e6, 2),
-            "tcp_scrape_floor_p50_us": round(gathered[0]["tcp_scrape_floor_p50"] * 1e6, 2),
             "allocate_p50_us_grpcio_client": round(p50_grpcio, 2),
             "allocate_p99_us_grpcio_client": round(_pct(allocs, 0.99) * 1e6, 2),
             "preferred_p50_us": round(_pct(prefs_native, 0.5) * 1e6, 2),
             "preferred_p99_us": round(_pct(prefs_native, 0.99) * 1e6, 2),
-            "preferred_server_mean_us": (round(gathered[0]["server_preferred_mean_s"] * 1e6, 3)
-                                         if gathered[0].get("server_preferred_mean_s") else None),
             "preferred_p50_us_grpcio_client": round(_pct(prefs, 0.5) * 1e6, 2),
             "scrape_p50_us": round(_pct(scrapes, 0.5) * 1e6, 2),
             "scrape_rps": round(len(scrapes) / scrape_t, 1) if scrape_t > 0 else None,
             "scrape_p99_us": round(_pct(scrapes, 0.99) * 1e6, 2),
-            # the daemon's own time per /metrics answer (render + the sendmsg that hands it over)
-            "scrape_server_mean_us": (round(gathered[0]["server_scrape_mean_s"] * 1e6, 3)
-                                      if gathered[0].get("server_scrape_mean_s") else None),
             "scrapes": len(scrapes),
-            # where each Allocate's client and daemon worker ran relative to each other, the
-            # bare exchange between the client's CPU and one CPU of each relation, and the host
-            "placement": {"allocate_by_relation": gathered[0].get("placement"),
-                          "client_cpus": gathered[0].get("client_cpus"), "worker_cpus": gathered[0].get("worker_cpus"),
-                          "floor_spin_by_relation": gathered[0].get("placement_floor")},
-            "host": gathered[0].get("host"),
             "allocate_calls": len(allocs) + len(allocs_native),
             "metrics_bytes": gathered[0]["body"],
-            "canary": ({"arch": can[0]["arch"], "hbm_read_gbps": round(min(c["read_gbps"] for c in can), 1),
-                        "hbm_write_gbps": round(min(c["write_gbps"] for c in can), 1),
-                        "mfma_bf16_tflops": round(min(c["mfma_tflops"] for c in can), 1),
-                        "lds_gemm_bf16_tflops": round(min(c["gemm_tflops"] for c in can), 1),
-                        "mfma_mxfp8_tflops": round(min(c["fp8_tflops"] for c in can), 1),
-                        "mfma_mxfp4_tflops": round(min(c["fp4_tflops"] for c in can), 1),
-                        "lds_march_kb": min(c["lds_bytes"] for c in can) // 1024} if can else None),
+            "full": args.full,
         }
+        if args.full:
+            out.update(full_fields(gathered, n))
         print(json.dumps(out), flush=True)
     client.close()
     h2.close()

@@ -10,7 +10,7 @@ for i in $(seq 1 ${PAIRS:-4}); do
   k=${#trees[@]}
   for j in $(seq 0 $((k - 1))); do
     t=${trees[$(( (i + j) % k ))]}
-    (cd "$t" && timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-canary 2>/dev/null | tail -1 | python -c "
+    (cd "$t" && timeout -k 10 120 python bench.py --full --steps 20 --warmup 3 --no-canary 2>/dev/null | tail -1 | python -c "
 import json, sys
 d = json.loads(sys.stdin.read())
 print('$t', d['value'], d['allocate_p99_us'], d['uds_roundtrip_floor_spin_p50_us'], d['allocate_cold_p50_us'],

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT="$PWD/gpurun_out"
 mkdir -p "$OUT"
 for i in ${REPS:-1 2 3}; do
-  timeout -k 10 240 python bench.py --no-canary --steps 20 --warmup 3 > "$OUT/rep_$i.log" 2>&1 || exit $?
+  timeout -k 10 240 python bench.py --full --no-canary --steps 20 --warmup 3 > "$OUT/rep_$i.log" 2>&1 || exit $?
   grep '^{' "$OUT/rep_$i.log" | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('rep', $i, {k: d[k] for k in ('allocate_p50_us', 'allocate_p99_us', 'uds_roundtrip_floor_spin_p50_us', 'scrape_rps', 'scrape_p50_us', 'tcp_scrape_floor_p50_us')})"
 done
 if [ -n "${RANKS:-}" ]; then

@@ -19,7 +19,7 @@ for s in ${STEPS:-pytest smoke bench prof}; do
   case $s in
     pytest) step pytest_gpu 420 python -u -m pytest tests -x -v -m gpu -s -p no:cacheprovider --timeout 120 --timeout-method thread ;;
     smoke)  step smoke 240 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench)  step bench 300 python bench.py ${BENCH_ARGS:-} ;;
+    bench)  step bench 300 python bench.py --full ${BENCH_ARGS:-} ;;
     idle)   step idle_probe ${IDLE_TIMEOUT:-400} python -u scripts/idle_probe.py --gaps ${IDLE_GAPS:-0.001,0.01,0.1} --calls ${IDLE_CALLS:-300} --out "$OUT/idle_probe${IDLE_TAG:-}.json" ;;
     soak)   step soak $(( ${SOAK_SECONDS:-120} + 120 )) python -u scripts/soak.py --seconds ${SOAK_SECONDS:-120} --backend amdsmi ;;
     suite)  step suite 600 python -m k8s_gpu_device_plugin_amd.benchmark.suite --json "$OUT/baseline_suite_gpu.json" ;;

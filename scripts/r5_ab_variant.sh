@@ -9,7 +9,7 @@ for i in 1 2 3; do
   for arm in cur variant; do
     echo "=== bench $arm #$i ($(date +%T))"
     if [ $arm = variant ]; then export AMDGPU_DP_NATIVE_SO="$PWD/$AB_SO"; else unset AMDGPU_DP_NATIVE_SO; fi
-    timeout -k 10 300 python bench.py > "$OUT/bench_ab_$arm.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full > "$OUT/bench_ab_$arm.log" 2>&1 || exit $?
     tail -1 "$OUT/bench_ab_$arm.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())

@@ -10,7 +10,7 @@ for i in 1 2 3 4; do
   for arm in default kw1; do
     if [ $arm = kw1 ]; then cfg='{"grpc": {"keepWarmMs": 1, "idleWakeMs": 0}}'; else cfg=''; fi
     echo "=== bench $arm #$i ($(date +%T))"
-    timeout -k 10 300 python bench.py ${cfg:+--daemon-config "$cfg"} > "$OUT/bench_def_$arm.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full ${cfg:+--daemon-config "$cfg"} > "$OUT/bench_def_$arm.log" 2>&1 || exit $?
     tail -1 "$OUT/bench_def_$arm.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())

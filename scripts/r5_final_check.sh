@@ -12,7 +12,7 @@ tail -1 "$OUT/smoke.log"
 : > "$OUT/final_bench.jsonl"
 for i in 1 2 3; do
   echo "=== bench #$i ($(date +%T))"
-  timeout -k 10 300 python bench.py > "$OUT/bench_final_$i.log" 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full > "$OUT/bench_final_$i.log" 2>&1 || exit $?
   tail -1 "$OUT/bench_final_$i.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())

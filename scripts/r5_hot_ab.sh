@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for i in 1 2 3 4; do
   for v in false true; do
     echo "=== bench hot=$v #$i ($(date +%T))"
-    timeout -k 10 300 python bench.py --daemon-config "{\"grpc\": {\"hotRecvPoll\": $v}}" > "$OUT/bench_hot_$v.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --daemon-config "{\"grpc\": {\"hotRecvPoll\": $v}}" > "$OUT/bench_hot_$v.log" 2>&1 || exit $?
     tail -1 "$OUT/bench_hot_$v.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); t = d['allocate_tail']

@@ -6,7 +6,7 @@ OUT="$PWD/gpurun_out/r5"
 mkdir -p "$OUT"
 for tag in kw1a kw1b; do
   echo "=== bench $tag ($(date +%T))"
-  timeout -k 10 300 python bench.py > "$OUT/bench_$tag.log" 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full > "$OUT/bench_$tag.log" 2>&1 || exit $?
   tail -1 "$OUT/bench_$tag.log" | cut -c1-160
 done
 echo "=== idle A/B x2 ($(date +%T))"

@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 : > "$OUT/prefault_bench.jsonl"
 for i in 1 2 3 4; do
   echo "=== bench #$i ($(date +%T))"
-  timeout -k 10 300 python bench.py > "$OUT/bench_prefault_$i.log" 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full > "$OUT/bench_prefault_$i.log" 2>&1 || exit $?
   tail -1 "$OUT/bench_prefault_$i.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); t = d['allocate_tail']

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 for i in 1 2 3; do
   for s in batch normal; do
     echo "=== bench backgroundSched=$s #$i ($(date +%T))"
-    timeout -k 10 300 python bench.py --daemon-config "{\"backgroundSched\": \"$s\"}" > "$OUT/bench_sched_$s.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --daemon-config "{\"backgroundSched\": \"$s\"}" > "$OUT/bench_sched_$s.log" 2>&1 || exit $?
     tail -1 "$OUT/bench_sched_$s.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); t = d['allocate_tail']

@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for i in 1 2 3; do
   for ms in 1000 100000; do
     echo "=== bench telemetry=${ms}ms #$i ($(date +%T))"
-    timeout -k 10 300 python bench.py --daemon-config "{\"telemetry\": {\"intervalMs\": $ms}}" > "$OUT/bench_tel_$ms.log" 2>&1 || exit $?
+    timeout -k 10 300 python bench.py --full --daemon-config "{\"telemetry\": {\"intervalMs\": $ms}}" > "$OUT/bench_tel_$ms.log" 2>&1 || exit $?
     tail -1 "$OUT/bench_tel_$ms.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read()); t = d['allocate_tail']

@@ -11,7 +11,7 @@ ARMS='{"kw1": {"grpc": {"keepWarmMs": 1, "idleWakeMs": 0}}, "kw10wake1": {"grpc"
 for arm in kw1 kw10wake1 kw10; do
   cfg=$(python3 -c "import json,sys; print(json.dumps(json.loads(sys.argv[1])[sys.argv[2]]))" "$ARMS" "$arm")
   echo "=== bench $arm ($(date +%T))"
-  timeout -k 10 300 python bench.py --daemon-config "$cfg" > "$OUT/bench_$arm.log" 2>&1 || exit $?
+  timeout -k 10 300 python bench.py --full --daemon-config "$cfg" > "$OUT/bench_$arm.log" 2>&1 || exit $?
   tail -1 "$OUT/bench_$arm.log" | python3 -c "
 import json, sys
 d = json.loads(sys.stdin.read())

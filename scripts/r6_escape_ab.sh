@@ -9,7 +9,7 @@ mkdir -p $out
 for i in $(seq 1 ${2:-3}); do
   for arm in off on; do
     flag=false; [ $arm = on ] && flag=true
-    timeout -k 10 200 python bench.py --steps 20 --warmup 5 --daemon-config "{\"grpc\": {\"coreEscape\": $flag}}" \
+    timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --daemon-config "{\"grpc\": {\"coreEscape\": $flag}}" \
       > $out/bench_${tag}_${arm}_$i.json 2> $out/bench_${tag}_${arm}_$i.err || exit 1
     python3 -c "
 import json

@@ -14,7 +14,7 @@ timeout -k 10 240 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/${t
 tail -1 "$OUT/${tag}_smoke.log"
 for i in 1 2; do
   echo "=== bench #$i ($(date +%T))"
-  timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${tag}_bench_$i.json" 2> "$OUT/${tag}_bench_$i.err" || exit $?
+  timeout -k 10 300 python bench.py --full --gpus 1 --steps 20 --warmup 5 > "$OUT/${tag}_bench_$i.json" 2> "$OUT/${tag}_bench_$i.err" || exit $?
   python3 -c "
 import json
 d = json.loads(open('$OUT/${tag}_bench_$i.json').read().strip().splitlines()[-1])

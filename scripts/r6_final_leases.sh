@@ -8,7 +8,7 @@ tag=${1:-final}
 out=gpurun_out/r6
 mkdir -p $out
 for i in 1 2 3; do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $out/bench_${tag}_$i.json 2> $out/bench_${tag}_$i.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $out/bench_${tag}_$i.json 2> $out/bench_${tag}_$i.err || exit 1
   python3 -c "
 import json
 d = json.loads(open('$out/bench_${tag}_$i.json').read().strip().splitlines()[-1])

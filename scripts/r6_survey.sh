@@ -8,9 +8,9 @@ tag=${1:-lease}
 out=gpurun_out/r6
 mkdir -p $out
 for i in 1 2; do
-  timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-canary > $out/bench_${tag}_$i.json 2> $out/bench_${tag}_$i.err || exit 1
+  timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-canary > $out/bench_${tag}_$i.json 2> $out/bench_${tag}_$i.err || exit 1
 done
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 --no-canary --daemon-config '{"grpc": {"activeWindowMs": 0}}' \
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 --no-canary --daemon-config '{"grpc": {"activeWindowMs": 0}}' \
   > $out/bench_${tag}_always.json 2> $out/bench_${tag}_always.err || exit 1
 timeout -k 10 120 python scripts/idle_wakeups.py --out $out/idle_wakeups_${tag}.json > $out/idle_wakeups_${tag}.log 2>&1 || exit 1
 timeout -k 10 120 python scripts/idle_wakeups.py --daemon-config '{"grpc": {"activeWindowMs": 0}}' \

@@ -32,6 +32,16 @@ def plugin_dir():
 
 
 @pytest.fixture
+def sock_dir():
+    # a second short directory, for the other unix sockets of a test (pytest's tmp_path
+    # grows with the user's name and the test's, past the 108 bytes a socket path may have)
+    d = tempfile.mkdtemp(prefix="dps-", dir="/tmp")
+    yield d
+    import shutil
+    shutil.rmtree(d, ignore_errors=True)
+
+
+@pytest.fixture
 def make_cfg(plugin_dir):
     from k8s_gpu_device_plugin_amd import config as config_mod
 

@@ -112,7 +112,7 @@ class _Allocator(threading.Thread):
                                                                         ("4gpu_spx", "none", "native", "0-2", False),
                                                                         ("4gpu_spx", "none", "native", "", True),
                                                                         ("4gpu_cpx", "single", "native", "0-2", True)])
-def test_random_fault_mix_converges(make_cfg, plugin_dir, tmp_path, seed, fixture, strategy, server, devices,
+def test_random_fault_mix_converges(make_cfg, plugin_dir, sock_dir, seed, fixture, strategy, server, devices,
                                     serialised):
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
     n = native.load()
@@ -124,7 +124,7 @@ def test_random_fault_mix_converges(make_cfg, plugin_dir, tmp_path, seed, fixtur
     shown = range(NGPU - 1) if devices else range(NGPU)  # the GPUs `devices` advertises (all but the last)
     ids = sorted(p.id for g in gpus if g.index in shown for p in g.partitions)  # one device per partition
     id_of_slot = {g.index: g.partitions[0].id for g in gpus}
-    podsock = str(tmp_path / "pod-resources" / "kubelet.sock")
+    podsock = os.path.join(sock_dir, "pod-resources", "kubelet.sock")
     pods = PodResourcesStub(podsock).start()
     cfg = make_cfg(fixture=fixture, migStrategy=strategy, grpc={"server": server}, telemetry={"intervalMs": 30},
                    rediscoverIntervalS=0.2, retrySeconds=0.2, devices=devices,

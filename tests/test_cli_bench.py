@@ -121,9 +121,29 @@ def _check_contract(r, n, steps, warmup):
     assert set(r["config"]) >= {"model", "global_batch", "seq_len", "parallelism"}
 
 
-def test_bench_single_rank():
-    r = _run_bench(["--steps", "2", "--warmup", "1"])
+def test_bench_single_rank(tmp_path):
+    """A plain run: the contract's fields from the timed steps alone (nothing of --full),
+    and with --dump-outputs the answers of the last timed step, the same from run to run."""
+    import numpy as np
+
+    from k8s_gpu_device_plugin_amd.api import v1beta1
+    r = _run_bench(["--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")])
     _check_contract(r, 1, 2, 1)
+    assert r["full"] is False and r["allocate_calls"] == 2 * 2 * 256
+    assert not {"allocate_tail", "canary", "host", "placement", "uds_roundtrip_floor_p50_us",
+                "allocate_cold_p50_us", "preferred_allocator_8gpu_size4_p50_us"} & set(r)
+    names = ["allocate_response", "allocate_response_h2", "preferred_response", "preferred_response_h2"]
+    assert sorted(os.listdir(tmp_path / "a")) == [x + ".npy" for x in names]
+    a = {x: np.load(tmp_path / "a" / (x + ".npy")) for x in names}
+    assert all(v.dtype == np.float32 and v.ndim == 1 and v.size for v in a.values())
+    # both clients were answered alike, and the answer is the allocation of one device
+    assert np.array_equal(a["allocate_response"], a["allocate_response_h2"])
+    assert np.array_equal(a["preferred_response"], a["preferred_response_h2"])
+    resp = v1beta1.AllocateResponse.FromString(a["allocate_response"].astype(np.uint8).tobytes())
+    assert len(resp.container_responses) == 1 and resp.container_responses[0].devices
+    _run_bench(["--steps", "1", "--warmup", "0", "--dump-outputs", str(tmp_path / "b")])
+    for x in names:  # another run, another number of steps: the same inputs, the same answers
+        assert np.array_equal(a[x], np.load(tmp_path / "b" / (x + ".npy"))), x
 
 
 @pytest.mark.slow
@@ -183,7 +203,8 @@ def test_bench_refuses_rank_gpu_mismatch():
 
 
 def test_bench_reports_advertised_devices_and_tail():
-    r = _run_bench(["--steps", "2", "--warmup", "1"])
+    r = _run_bench(["--steps", "2", "--warmup", "1", "--full"])
+    assert r["full"] is True
     assert r["advertised_devices"] == 1 and r["world_size"] == 1
     t = r["allocate_tail"]
     # every slow call has exactly one cause; with the daemon's call trace each call is
@@ -223,7 +244,7 @@ def test_inspect_prints_the_node_and_its_placements(tmp_path):
     assert not feature.exists() and not (tmp_path / "dp").exists()
 
 
-def test_bench_daemon_exits_with_a_harness_that_dies(tmp_path):
+def test_bench_daemon_exits_with_a_harness_that_dies(sock_dir):
     """A benchmark or probe killed mid-run (timeout, OOM, an exception before its
     cleanup) must not leave its plugin daemon running: the daemon is told its parent's
     pid (AMDGPU_DP_PARENT_PID) and gets SIGTERM when that parent exits."""
@@ -233,7 +254,7 @@ def test_bench_daemon_exits_with_a_harness_that_dies(tmp_path):
         "import bench\n"
         "proc, kubelet, port, reg, backend = bench.start_daemon(1, 'native', %r, backend='fixture')\n"
         "print(proc.pid, flush=True)\n"
-        "os._exit(0)\n" % (ROOT, str(tmp_path)))
+        "os._exit(0)\n" % (ROOT, sock_dir))
     out = subprocess.run([sys.executable, "-c", script], capture_output=True, text=True, timeout=90, cwd=ROOT)
     pid = int(out.stdout.strip().splitlines()[-1])
     deadline = time.monotonic() + 15
@@ -260,7 +281,7 @@ def test_bench_daemon_exits_with_a_harness_that_dies(tmp_path):
         except OSError:
             pass
     os.kill(pid, signal.SIGKILL)
-    with open(tmp_path / "daemon.log") as f:
+    with open(os.path.join(sock_dir, "daemon.log")) as f:
         tail = f.read()[-3000:]
     raise AssertionError("daemon %d outlived its harness\n%s\n%s\n%s" % (pid, "\n".join(status), "\n".join(threads),
                                                                           tail))

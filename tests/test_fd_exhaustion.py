@@ -57,8 +57,8 @@ def _connect(kind, addr):
 
 
 @pytest.mark.parametrize("kind", ["http", "grpc"])
-def test_server_sheds_instead_of_spinning_when_out_of_fds(kind, tmp_path):
-    p = subprocess.Popen([sys.executable, "-c", CHILD % {"root": ROOT}, kind, str(tmp_path)], stdin=subprocess.PIPE,
+def test_server_sheds_instead_of_spinning_when_out_of_fds(kind, sock_dir):
+    p = subprocess.Popen([sys.executable, "-c", CHILD % {"root": ROOT}, kind, sock_dir], stdin=subprocess.PIPE,
                          stdout=subprocess.PIPE, text=True)
     try:
         addr = json.loads(p.stdout.readline())["addr"]

@@ -919,12 +919,12 @@ def _lit(name, value):  # HPACK literal without indexing, new name
 
 
 @pytest.mark.parametrize("last_sid", [0x7FFFFFFF, 0])
-def test_client_honours_goaway_last_stream_id(n, tmp_path, last_sid):
+def test_client_honours_goaway_last_stream_id(n, sock_dir, last_sid):
     """A GOAWAY that still covers the request (a gRPC server shutting down gracefully
     sends last = 2^31-1 and then answers what it took) does not fail the call; one below
     the request's stream says it was not processed, so the caller may send it again
     (plugin.register does, once)."""
-    path = str(tmp_path / "h2.sock")
+    path = os.path.join(sock_dir, "h2.sock")
     goaway = _frame(7, 0, 0, struct.pack(">II", last_sid, 0))
     answer = (_frame(1, 0x4, 1, b"\x88" + _lit(b"content-type", b"application/grpc"))
               + _frame(0, 0, 1, b"\x00\x00\x00\x00\x00")

@@ -526,12 +526,12 @@ def test_reset_state_survives_a_reload(make_cfg, plugin_dir, run_manager):
         assert _wait(lambda: m.plugins[0].table.healthy_count() == 2)
 
 
-def test_pod_resources_allocation_metric(make_cfg, plugin_dir, run_manager, tmp_path):
+def test_pod_resources_allocation_metric(make_cfg, plugin_dir, run_manager, sock_dir):
     """podResources.enabled: the kubelet PodResources List is polled and every held
     device of ours appears as allocation_info{namespace,pod,container}; other vendors'
     resources are ignored; a kubelet outage flips pod_resources_up to 0."""
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
-    sock = str(tmp_path / "pod-resources" / "kubelet.sock")
+    sock = os.path.join(sock_dir, "pod-resources", "kubelet.sock")
     stub = PodResourcesStub(sock).start()
     try:
         with KubeletStub(plugin_dir) as k:
@@ -851,12 +851,12 @@ def test_halfrate_fixture_is_discovered_degraded(n):
     assert NodeTopology(gpus, topo).degraded_links() == [(0, 1)]
 
 
-def test_pod_resources_feed_link_load_to_the_allocator(make_cfg, plugin_dir, run_manager, tmp_path):
+def test_pod_resources_feed_link_load_to_the_allocator(make_cfg, plugin_dir, run_manager, sock_dir):
     """CPX: a running pod holds partitions on GPUs 0 and 1 (PodResources).  The tables'
     topology counts it on link 0-1, /metrics shows it, and a new 2-GPU pod is placed off
     that link."""
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
-    sock = str(tmp_path / "pod-resources" / "kubelet.sock")
+    sock = os.path.join(sock_dir, "pod-resources", "kubelet.sock")
     stub = PodResourcesStub(sock).start()
     try:
         with KubeletStub(plugin_dir) as k:
@@ -878,12 +878,12 @@ def test_pod_resources_feed_link_load_to_the_allocator(make_cfg, plugin_dir, run
         stub.stop()
 
 
-def test_pod_link_load_uses_the_whole_node_topology(make_cfg, plugin_dir, run_manager, tmp_path):
+def test_pod_link_load_uses_the_whole_node_topology(make_cfg, plugin_dir, run_manager, sock_dir):
     """`devices` advertises GPUs 0-2 of a 4-GPU node: the tables' topology still spans all
     4 GPUs, so a pod on GPUs 1 and 2 must land on link 1-2 (a row stride of 3 put it on
     1-1 and 1-3)."""
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
-    sock = str(tmp_path / "pod-resources" / "kubelet.sock")
+    sock = os.path.join(sock_dir, "pod-resources", "kubelet.sock")
     stub = PodResourcesStub(sock).start()
     try:
         with KubeletStub(plugin_dir) as k:
@@ -993,12 +993,12 @@ def test_native_server_crash_loop_is_fatal(make_cfg, plugin_dir):
             t.join(10)
 
 
-def test_allocate_counts_as_link_load_until_pod_resources_has_it(make_cfg, plugin_dir, run_manager, tmp_path):
+def test_allocate_counts_as_link_load_until_pod_resources_has_it(make_cfg, plugin_dir, run_manager, sock_dir):
     """The plugin answers a multi-GPU Allocate: the link it spans counts as used at
     once, before the PodResources poll; after the next poll the count comes from the
     kubelet's map instead (not both)."""
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
-    sock = str(tmp_path / "pod-resources" / "kubelet.sock")
+    sock = os.path.join(sock_dir, "pod-resources", "kubelet.sock")
     stub = PodResourcesStub(sock).start()
     try:
         with KubeletStub(plugin_dir) as k:
