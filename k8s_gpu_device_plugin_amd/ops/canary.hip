@@ -19,6 +19,8 @@
 //      per block (one per SIMD), 8 blocks per CU -> dense bf16 TFLOP/s.
 //   4. Matrix path       - LDS-staged MFMA GEMM on exact integer data, ABFT-checked.
 //   5. fp8 / bf8 / fp4 MFMA exactness and rate, LDS march (datapath.hip).
+//   6. Site probe        - MFMA and vector-ALU exactness on every CU and SIMD, with the
+//      place of each mismatch (sites.hip).
 //
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
 #include <hip/hip_runtime.h>
@@ -45,15 +47,6 @@ __device__ __forceinline__ uint4 pattern(uint64_t idx, uint32_t seed) {
 
 __device__ __forceinline__ uint32_t diff(const uint4& a, const uint4& b) {
   return (a.x != b.x) + (a.y != b.y) + (a.z != b.z) + (a.w != b.w);
-}
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
-__device__ __forceinline__ short bf16_of_int(int v) {
-  const float f = static_cast<float>(v);
-  uint32_t u;
-  __builtin_memcpy(&u, &f, 4);
-  return static_cast<short>(u >> 16);  // exact for small integers
 }
 
 // One wave per block computes C[32x32] = A[32xK] * B[Kx32] with K = 16 * ksteps, then
@@ -835,6 +828,13 @@ struct amdgpu_canary_result {
   unsigned long long lowp_errors;       // fp8 / bf8 / fp4 MFMA exactness mismatches
   unsigned long long lds_errors;        // LDS march mismatches
   unsigned long long lds_bytes;         // LDS bytes per workgroup the march covered
+  unsigned long long site_errors;       // site probe (sites.hip): wrong mfma + lowp + valu results + unlocated
+  int cus_reached;                      // CUs the site probe ran on
+  int simds_reached;                    // (CU, SIMD) sites it ran on
+  int cus_unreached;                    // num_cus - cus_reached: reported, does not fail the run
+  double site_ms;                       // device time of the site probe's launches
+  int n_bad_sites;                      // sites with a wrong result
+  unsigned int bad_sites[16];           // the first 16 of them, packed (canary_common.h)
 };
 
 struct amdgpu_canary_datapath_result {  // datapath.hip
@@ -954,8 +954,30 @@ int amdgpu_canary_run(int device, unsigned long long hbm_bytes, int passes, int 
     out->lds_errors = dp.lds_errors;
     out->lds_bytes = dp.lds_bytes;
   }
+  // where the matrix cores and the vector ALU compute: every CU and SIMD, mismatches located
+  {
+    amdgpu_canary_sites_result sr;
+    if (amdgpu_canary_sites(device, 0, 4, -1, 0, nullptr, nullptr, 0, &sr, out->error, sizeof(out->error)) != 0)
+      goto done;
+    out->site_errors = sr.errors[0] + sr.errors[1] + sr.errors[2] + sr.unlocated_errors;
+    out->cus_reached = sr.cus_reached;
+    out->simds_reached = sr.simds_reached;
+    out->cus_unreached = sr.cus_expected > sr.cus_reached ? sr.cus_expected - sr.cus_reached : 0;
+    out->site_ms = sr.ms;
+    out->n_bad_sites = sr.n_bad;
+    std::memcpy(out->bad_sites, sr.bad_sites, sizeof(out->bad_sites));
+    if (out->site_errors > 0) {
+      char where[64] = "an unknown site";  // every wrong wave moved while it ran
+      if (sr.n_bad > 0) amdgpu_canary_format_site(sr.bad_sites[0], where, sizeof(where));
+      int len = std::snprintf(out->error, sizeof(out->error), "site check: %llu wrong results at %s", out->site_errors,
+                              where);
+      if (sr.n_bad > 1)
+        std::snprintf(out->error + len, sizeof(out->error) - len, " (+%d more site%s)", sr.n_bad - 1,
+                      sr.n_bad > 2 ? "s" : "");
+    }
+  }
   out->ok = (out->hbm_errors == 0 && out->mfma_errors == 0 && out->gemm_errors == 0 && out->lowp_errors == 0 &&
-             out->lds_errors == 0)
+             out->lds_errors == 0 && out->site_errors == 0)
                 ? 1
                 : 0;
 done:

@@ -3,12 +3,14 @@
 ``run(device)`` loads ``libamdgpu_canary.so`` with ctypes (no torch needed) and runs
 the HBM pattern test, the MFMA exactness/throughput probe, the matrix-path check
 (an LDS-staged MFMA GEMM on exact integer data with ABFT row/column checksums), the
-fp8 / bf8 / fp4 MFMA exactness and rate checks and the LDS march (``datapath.hip``) on
+fp8 / bf8 / fp4 MFMA exactness and rate checks, the LDS march (``datapath.hip``) and the
+site probe (``sites.hip``: MFMA and vector-ALU exactness on every CU and SIMD, each
+mismatch located) on
 one HIP device (= one compute partition).  ``run_isolated(device)`` does the same in a child process so the
 long-lived plugin daemon never creates a HIP context on GPUs it hands to pods.
 
 CLI: ``python -m k8s_gpu_device_plugin_amd.ops.canary --device 0 [--bytes N]`` prints
-one JSON line.  Missing library => loud ``RuntimeError`` (never a silent pass).
+one JSON line; ``--sites`` prints the site probe's coverage map instead.  Missing library => loud ``RuntimeError`` (never a silent pass).
 """
 from __future__ import annotations
 
@@ -30,7 +32,37 @@ class CanaryResult(ctypes.Structure):
                 ("error", ctypes.c_char * 256), ("gemm_tflops", ctypes.c_double),
                 ("gemm_errors", ctypes.c_ulonglong), ("fp8_tflops", ctypes.c_double),
                 ("fp4_tflops", ctypes.c_double), ("lowp_errors", ctypes.c_ulonglong),
-                ("lds_errors", ctypes.c_ulonglong), ("lds_bytes", ctypes.c_ulonglong)]
+                ("lds_errors", ctypes.c_ulonglong), ("lds_bytes", ctypes.c_ulonglong),
+                ("site_errors", ctypes.c_ulonglong), ("cus_reached", ctypes.c_int),
+                ("simds_reached", ctypes.c_int), ("cus_unreached", ctypes.c_int), ("site_ms", ctypes.c_double),
+                ("n_bad_sites", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16)]
+
+
+SITE_SLOTS = 1 << 14
+SITE_CHECKS = ("mfma", "lowp", "valu")
+
+
+class SiteSlot(ctypes.Structure):
+    _fields_ = [("waves", ctypes.c_uint), ("bad", ctypes.c_uint * 3)]
+
+
+class SitesResult(ctypes.Structure):
+    _fields_ = [("errors", ctypes.c_ulonglong * 3), ("unlocated_errors", ctypes.c_ulonglong),
+                ("waves", ctypes.c_ulonglong), ("moved", ctypes.c_ulonglong), ("launches", ctypes.c_int),
+                ("cus_reached", ctypes.c_int), ("simds_reached", ctypes.c_int), ("cus_expected", ctypes.c_int),
+                ("n_bad", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16), ("ms", ctypes.c_double)]
+
+
+def decode_site(packed: int) -> dict:
+    """Fields of a packed site: simd bits 1:0, cu 5:2, sh 6, se 9:7, xcc 13:10 (the layout
+    ``site_id()`` in ``ops/sites.hip`` builds from HW_REG_HW_ID and HW_REG_XCC_ID)."""
+    p = int(packed)
+    return {"xcc": (p >> 10) & 0xF, "se": (p >> 7) & 0x7, "sh": (p >> 6) & 0x1, "cu": (p >> 2) & 0xF, "simd": p & 0x3}
+
+
+def format_site(packed: int) -> str:
+    """``xcc3/se1/sh0/cu7/simd2``: XCD, shader engine, shader array, CU within it, SIMD."""
+    return "xcc%(xcc)d/se%(se)d/sh%(sh)d/cu%(cu)d/simd%(simd)d" % decode_site(packed)
 
 
 _lib = None
@@ -77,6 +109,11 @@ def load():
         lib.amdgpu_canary_lowp_gemm.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
             [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int]
         lib.amdgpu_canary_lowp_gemm.restype = ctypes.c_int
+        lib.amdgpu_canary_sites.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(SiteSlot),
+                                                                 ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
+                                                                 ctypes.POINTER(SitesResult), ctypes.c_char_p,
+                                                                 ctypes.c_int]
+        lib.amdgpu_canary_sites.restype = ctypes.c_int
         _lib = lib
     return _lib
 
@@ -92,6 +129,38 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     out["arch"] = r.arch.decode(errors="replace")
     out["error"] = r.error.decode(errors="replace")
     out["ok"] = bool(r.ok) and rc == 0
+    out["bad_sites"] = [format_site(p) for p in r.bad_sites[:min(r.n_bad_sites, 16)]]
+    return out
+
+
+def site_probe(device: int = 0, blocks: int = 0, ksteps: int = 4, inject=None, inject_waves: int = 0) -> dict:
+    """Coverage map and fault location of the MFMA and vector-ALU exactness checks: 4-wave
+    workgroups, one resident per CU, whose waves record the (xcc, se, sh, cu, simd) they ran
+    on.  ``blocks=0``: 2 workgroups per CU plus up to 3 top-up launches while a CU or SIMD is
+    missing; ``blocks>0``: one launch of that many.  ``inject`` (``mfma``, ``lowp`` or
+    ``valu``) makes the first ``inject_waves`` waves compute that check on a perturbed
+    operand.  Returns the totals, ``sites`` (every site a wave ran on) and ``wave_sites``
+    (the site of each wave of the first launch)."""
+    check = -1 if inject is None else SITE_CHECKS.index(inject)
+    lib = load()
+    r = SitesResult()
+    table = (SiteSlot * SITE_SLOTS)()
+    n_waves = 4 * (int(blocks) if blocks > 0 else 2 * 1024)  # automatic: room for 1024 CUs
+    wave_sites = (ctypes.c_uint * n_waves)()
+    err = ctypes.create_string_buffer(256)
+    rc = lib.amdgpu_canary_sites(int(device), int(blocks), int(ksteps), check, int(inject_waves), table, wave_sites,
+                                 n_waves, ctypes.byref(r), err, 256)
+    if rc != 0:
+        raise RuntimeError("site_probe failed: " + err.value.decode(errors="replace"))
+    out = {name: int(r.errors[i]) for i, name in enumerate(SITE_CHECKS)}
+    for f in ("unlocated_errors", "waves", "moved", "launches", "cus_reached", "simds_reached", "cus_expected"):
+        out[f] = int(getattr(r, f))
+    out["n_bad"] = int(r.n_bad)
+    out["bad_sites"] = [format_site(p) for p in r.bad_sites[:min(r.n_bad, 16)]]
+    out["ms"] = r.ms
+    out["sites"] = {format_site(p): dict({"waves": int(s.waves)}, **{c: int(s.bad[i]) for i, c in enumerate(SITE_CHECKS)})
+                    for p, s in enumerate(table) if s.waves}
+    out["wave_sites"] = [format_site(p) for p in wave_sites if p != 0xFFFFFFFF]  # unwritten entries stay all-ones
     return out
 
 
@@ -282,7 +351,12 @@ def main(argv=None) -> int:
     ap.add_argument("--gemm-iters", type=int, default=20)
     ap.add_argument("--gemm-kernel", choices=sorted(GEMM_KERNELS), default="auto")
     ap.add_argument("--gemm-random", action="store_true", help="random bf16 operands (rate only, no checksum)")
+    ap.add_argument("--sites", action="store_true", help="only the site probe: the CU/SIMD coverage map")
     a = ap.parse_args(argv)
+    if a.sites:
+        res = site_probe(a.device)
+        print(json.dumps(res))
+        return 0 if not (res["mfma"] or res["lowp"] or res["valu"] or res["unlocated_errors"]) else 1
     if a.gemm:
         res = gemm_rate(a.device, a.gemm, a.gemm, a.gemm, a.gemm_iters, kernel=a.gemm_kernel,
                         random_data=a.gemm_random)

@@ -1,5 +1,6 @@
-// Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip): the hash
-// that derives exact small-integer operands, and the MFMA register vector types.
+// Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip, sites.hip): the
+// hash that derives exact small-integer operands, the MFMA register vector types, the
+// bf16 / OCP low-precision operand packing, and the site probe's C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,4 +34,88 @@ __device__ __forceinline__ int b_val(uint32_t blk, int k, int col) {
                    static_cast<uint64_t>(col) ^ (1ull << 62));
 }
 
+using bf16x8 = __attribute__((ext_vector_type(8))) short;
+
+__device__ __forceinline__ short bf16_of_int(int v) {
+  const float f = static_cast<float>(v);
+  uint32_t u;
+  __builtin_memcpy(&u, &f, 4);
+  return static_cast<short>(u >> 16);  // exact for small integers
+}
+
+using i32x8 = __attribute__((ext_vector_type(8))) int;
+
+constexpr int kFp8 = 0, kBf8 = 1, kFp4 = 4;  // cbsz / blgp format codes
+constexpr int kFp8Unscaled = 8;             // host-side id of v_mfma_f32_32x32x16_fp8_fp8
+
+// OCP code of a small integer v in [-4, 4] (every one is exact in all three formats).
+template <int FMT>
+__device__ __forceinline__ uint32_t lowp_code(int v) {
+  const uint32_t m = static_cast<uint32_t>(v < 0 ? -v : v);
+  uint32_t c;
+  if (FMT == kFp8) c = m == 0 ? 0u : m == 1 ? 0x38u : m == 2 ? 0x40u : m == 3 ? 0x44u : 0x48u;       // e4m3fn
+  else if (FMT == kBf8) c = m == 0 ? 0u : m == 1 ? 0x3Cu : m == 2 ? 0x40u : m == 3 ? 0x42u : 0x44u;  // e5m2
+  else c = m == 0 ? 0u : m == 1 ? 0x2u : m == 2 ? 0x4u : m == 3 ? 0x5u : 0x6u;                       // e2m1
+  if (v < 0) c |= FMT == kFp4 ? 0x8u : 0x80u;
+  return c;
+}
+
+template <int FMT>
+constexpr int kBits = FMT == kFp4 ? 4 : 8;
+
+// k (within one 64-deep step) of element j of a lane in half h (layout note in datapath.hip)
+template <int FMT>
+__device__ __forceinline__ int kmap(int h, int j) {
+  return FMT == kFp4 ? 32 * h + j : 32 * (j >> 4) + 16 * h + (j & 15);
+}
+
+// element j (0..31) of a lane's operand
+template <int FMT>
+__device__ __forceinline__ void put(i32x8& x, int j, uint32_t code) {
+  constexpr int b = kBits<FMT>;
+  x[(j * b) >> 5] |= static_cast<int>(code << ((j * b) & 31));
+}
+
+// E8M0 block scale of (row or column `rc`, k-block `kb`, operand `which`) when varied:
+// 2^0 or 2^1, so every product stays an exact small integer in fp32.
+__device__ __forceinline__ int scale_exp(int vary, int rc, int kb, int which) {
+  return vary ? static_cast<int>(mix32((static_cast<uint64_t>(which) << 48) ^ (static_cast<uint64_t>(rc) << 24) ^
+                                       static_cast<uint64_t>(kb)) & 1u)
+              : 0;
+}
+
 }  // namespace canary
+
+// ---- site probe (sites.hip): where on the chip each exactness check ran ----------------
+// A site is (xcc, se, sh, cu, simd) packed into 14 bits:
+//   simd 1:0 | cu 5:2 | sh 6 | se 9:7 | xcc 13:10
+extern "C" {
+
+constexpr int kSiteSlots = 1 << 14;
+constexpr int kSiteChecks = 3;  // 0 mfma, 1 lowp, 2 valu
+
+struct amdgpu_canary_site_slot {  // one per packed site
+  unsigned int waves;             // waves that ran all three checks here
+  unsigned int bad[kSiteChecks];  // wrong results they found, per check
+};
+
+struct amdgpu_canary_sites_result {
+  unsigned long long errors[kSiteChecks];  // located wrong results per check
+  unsigned long long unlocated_errors;     // wrong results of waves that changed site while checking
+  unsigned long long waves;                // located waves
+  unsigned long long moved;                // waves that changed site while checking
+  int launches;
+  int cus_reached;    // distinct (xcc, se, sh, cu) with a located wave
+  int simds_reached;  // distinct sites with a located wave
+  int cus_expected;   // multiProcessorCount
+  int n_bad;          // sites with a wrong result
+  unsigned int bad_sites[16];  // the first 16 of them, packed
+  double ms;          // device time over all launches
+};
+
+int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, int inject_waves,
+                        amdgpu_canary_site_slot* table_out, unsigned int* wave_site_out, int wave_site_len,
+                        amdgpu_canary_sites_result* result, char* err, int err_len);
+int amdgpu_canary_format_site(unsigned int site, char* buf, int len);  // "xcc3/se1/sh0/cu7/simd2"
+
+}  // extern "C"

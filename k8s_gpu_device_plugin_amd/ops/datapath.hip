@@ -42,47 +42,7 @@
 
 namespace {
 
-using namespace canary;
-using i32x8 = __attribute__((ext_vector_type(8))) int;
-
-constexpr int kFp8 = 0, kBf8 = 1, kFp4 = 4;  // cbsz / blgp format codes
-constexpr int kFp8Unscaled = 8;             // host-side id of v_mfma_f32_32x32x16_fp8_fp8
-
-// OCP code of a small integer v in [-4, 4] (every one is exact in all three formats).
-template <int FMT>
-__device__ __forceinline__ uint32_t lowp_code(int v) {
-  const uint32_t m = static_cast<uint32_t>(v < 0 ? -v : v);
-  uint32_t c;
-  if (FMT == kFp8) c = m == 0 ? 0u : m == 1 ? 0x38u : m == 2 ? 0x40u : m == 3 ? 0x44u : 0x48u;       // e4m3fn
-  else if (FMT == kBf8) c = m == 0 ? 0u : m == 1 ? 0x3Cu : m == 2 ? 0x40u : m == 3 ? 0x42u : 0x44u;  // e5m2
-  else c = m == 0 ? 0u : m == 1 ? 0x2u : m == 2 ? 0x4u : m == 3 ? 0x5u : 0x6u;                       // e2m1
-  if (v < 0) c |= FMT == kFp4 ? 0x8u : 0x80u;
-  return c;
-}
-
-template <int FMT>
-constexpr int kBits = FMT == kFp4 ? 4 : 8;
-
-// k (within one 64-deep step) of element j of a lane in half h (see the layout note above)
-template <int FMT>
-__device__ __forceinline__ int kmap(int h, int j) {
-  return FMT == kFp4 ? 32 * h + j : 32 * (j >> 4) + 16 * h + (j & 15);
-}
-
-// element j (0..31) of a lane's operand
-template <int FMT>
-__device__ __forceinline__ void put(i32x8& x, int j, uint32_t code) {
-  constexpr int b = kBits<FMT>;
-  x[(j * b) >> 5] |= static_cast<int>(code << ((j * b) & 31));
-}
-
-// E8M0 block scale of (row or column `rc`, k-block `kb`, operand `which`) when varied:
-// 2^0 or 2^1, so every product stays an exact small integer in fp32.
-__device__ __forceinline__ int scale_exp(int vary, int rc, int kb, int which) {
-  return vary ? static_cast<int>(mix32((static_cast<uint64_t>(which) << 48) ^ (static_cast<uint64_t>(rc) << 24) ^
-                                       static_cast<uint64_t>(kb)) & 1u)
-              : 0;
-}
+using namespace canary;  // operand packing (lowp_code, kmap, put, scale_exp): canary_common.h
 
 template <int FMT>
 __global__ void __launch_bounds__(64) lowp_exact(int ksteps, int vary_scale, int inject_blocks,

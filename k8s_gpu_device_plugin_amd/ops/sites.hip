@@ -1,0 +1,346 @@
+// MI355X (gfx950 / CDNA4) health canary, part 3: the site probe.
+//
+// The exactness kernels of canary.hip and datapath.hip are grids of single-wave blocks:
+// nothing says that every CU takes one, a wave occupies one of a CU's four SIMDs (each
+// with its own matrix core), and a mismatch is counted, never located.  site_probe runs
+// the same kind of check as 4-wave workgroups that each take a CU's whole LDS, so one
+// workgroup is resident per CU at a time, and every wave records where it ran:
+//
+//   * site_id(): (xcc, se, sh, cu, simd) from HW_REG_HW_ID bits 15:4 and HW_REG_XCC_ID
+//     bits 3:0 (layout: hip/amd_detail/amd_device_functions.h above __smid()), packed into
+//     14 bits (canary_common.h).  Read before and after the checks; a wave whose site
+//     changed in between (context-switched to other hardware) is counted as moved and its
+//     errors as unlocated.
+//   * mfma: v_mfma_f32_32x32x16_bf16 on small integers, as mfma_exact (K = 16 * ksteps);
+//   * lowp: v_mfma_scale_f32_32x32x64_f8f6f4 in fp8 with varied power-of-two block scales,
+//     as lowp_exact<fp8> (K = 64 * ksteps);
+//   * valu: a fixed per-lane chain of 32-bit multiply-add / shift / rotate, 64-bit add,
+//     exact fp32 and fp64 FMA and a __shfl_xor butterfly, folded into one 32-bit digest
+//     per lane and compared with digests the HOST computed with the same function: a
+//     faulty SIMD cannot agree with itself.
+//
+// Lane 0 of each wave adds to table[site]; the host reads the table, counts the CUs and
+// SIMDs reached and launches again (at most 3 more times) while some are missing.
+// No spin-waits, no inter-workgroup communication, every loop bounded by a constant or an
+// argument.
+//
+// C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "canary_common.h"
+
+namespace {
+
+using namespace canary;
+
+constexpr int kProbeWaves = 4;   // waves per workgroup: one per SIMD of a CU
+constexpr int kMaxBlocks = 4096; // global wave index < 2^14
+constexpr int kMaxLdsBytes = 160 * 1024;
+constexpr int kValuRounds = 48;
+
+// s_getreg_b32 immediate: register id 5:0, bit offset 10:6, size - 1 15:11
+constexpr int kHwRegHwId = 4, kHwRegXccId = 20;
+constexpr int getreg_imm(int reg, int offset, int size) { return ((size - 1) << 11) | (offset << 6) | reg; }
+
+// HW_ID 15:4 = simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (3 bits: 14:13 on gfx942/950,
+// bit 15 reads 0 there).  cu, sh and se are contiguous, so they move as one 8-bit field.
+__device__ __forceinline__ uint32_t site_id() {
+  const uint32_t hw = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegHwId, 4, 12));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegXccId, 0, 4));
+  return ((hw & 3u) | (((hw >> 4) & 0xFFu) << 2) | ((xcc & 0xFu) << 10)) & (kSiteSlots - 1);
+}
+
+// ---- valu chain: the same code on host and device ----------------------------------
+struct valu_state {
+  uint32_t x;
+  uint64_t y;
+};
+
+__host__ __device__ inline uint32_t rotl32(uint32_t v, int s) { return (v << s) | (v >> (32 - s)); }
+
+__host__ __device__ inline valu_state valu_init(int lane) {
+  return {0x6A09E667u + 0x9E3779B1u * static_cast<uint32_t>(lane), 0xBB67AE8584CAA73Bull + static_cast<uint64_t>(lane)};
+}
+
+// One round up to the cross-lane exchange.  fp32: 12-bit * 11-bit + 8-bit < 2^24; fp64:
+// 24-bit * 24-bit + 20-bit < 2^53: every conversion, product and sum is exact.
+__host__ __device__ inline void valu_round(valu_state& s, int lane, int round) {
+  s.x = s.x * 0x85EBCA77u + static_cast<uint32_t>(lane * 64 + round);  // 32-bit multiply-add
+  s.x = rotl32(s.x, 7) ^ (s.x >> 3) ^ (s.x << 5);                      // rotate, shifts
+  s.y += (static_cast<uint64_t>(s.x) << 21) | static_cast<uint64_t>(round);  // 64-bit add
+  const float f = __builtin_fmaf(static_cast<float>(s.x & 0xFFFu), static_cast<float>((s.x >> 12) & 0x7FFu),
+                                 static_cast<float>(s.x >> 24));
+  s.x ^= static_cast<uint32_t>(f);
+  const double d = __builtin_fma(static_cast<double>(s.x & 0xFFFFFFu), static_cast<double>(s.y & 0xFFFFFFull),
+                                 static_cast<double>((s.y >> 44) & 0xFFFFFull));
+  s.y ^= static_cast<uint64_t>(d);
+}
+
+// fold in the x of lane ^ (1 << (round % 6))
+__host__ __device__ inline void valu_fold(valu_state& s, uint32_t other) { s.x += rotl32(other, 13); }
+
+__host__ __device__ inline uint32_t valu_digest(const valu_state& s) {
+  return s.x ^ static_cast<uint32_t>(s.y) ^ static_cast<uint32_t>(s.y >> 32);
+}
+
+void valu_expected(uint32_t* digest) {  // the 64 lanes of one wave, shuffle emulated over an array
+  valu_state s[kWave];
+  for (int l = 0; l < kWave; ++l) s[l] = valu_init(l);
+  for (int r = 0; r < kValuRounds; ++r) {
+    uint32_t x[kWave];
+    for (int l = 0; l < kWave; ++l) {
+      valu_round(s[l], l, r);
+      x[l] = s[l].x;
+    }
+    for (int l = 0; l < kWave; ++l) valu_fold(s[l], x[l ^ (1 << (r % 6))]);
+  }
+  for (int l = 0; l < kWave; ++l) digest[l] = valu_digest(s[l]);
+}
+
+// ---- the three checks: wrong results this lane sees --------------------------------
+__device__ __forceinline__ uint32_t check_mfma(uint32_t key, int lane, int ksteps, bool inject) {
+  const int r = lane & 31, h = lane >> 5;
+  f32x16 acc;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int s = 0; s < ksteps; ++s) {
+    bf16x8 a, b;
+    for (int j = 0; j < 8; ++j) {
+      const int k = s * 16 + 8 * h + j;  // lane l holds A[r][8h+j], B[8h+j][r]
+      a[j] = bf16_of_int(a_val(key, r, k) + ((s == 0 && j == 0 && lane == 0 && inject) ? 1 : 0));
+      b[j] = bf16_of_int(b_val(key, k, r));
+    }
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+  }
+  uint32_t bad = 0;
+  for (int reg = 0; reg < 16; ++reg) {
+    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;  // C/D map of 32x32x16
+    int ref = 0;
+    for (int k = 0; k < ksteps * 16; ++k) ref += a_val(key, row, k) * b_val(key, k, r);
+    bad += acc[reg] != static_cast<float>(ref);
+  }
+  return bad;
+}
+
+__device__ __forceinline__ uint32_t check_lowp(uint32_t key, int lane, int ksteps, bool inject) {
+  const int r = lane & 31, h = lane >> 5;
+  const uint32_t blk = key + (static_cast<uint32_t>(kFp8 + 1) << 20);  // as lowp_exact<kFp8>
+  f32x16 acc;
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  for (int s = 0; s < ksteps; ++s) {
+    i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+      const int k = 64 * s + kmap<kFp8>(h, j);
+      int av = a_val(blk, r, k);
+      if (s == 0 && j == 0 && lane == 0 && inject) av = av == 4 ? 3 : av + 1;
+      put<kFp8>(a, j, lowp_code<kFp8>(av));
+      put<kFp8>(b, j, lowp_code<kFp8>(b_val(blk, k, r)));
+    }
+    const int sa = 127 + scale_exp(1, r, 2 * s + h, 0);
+    const int sb = 127 + scale_exp(1, r, 2 * s + h, 1);
+    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, kFp8, kFp8, 0, sa, 0, sb);
+  }
+  uint32_t bad = 0;
+  for (int reg = 0; reg < 16; ++reg) {
+    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    int ref = 0;
+    for (int kb = 0; kb < 2 * ksteps; ++kb) {
+      int part = 0;
+      for (int j = 0; j < 32; ++j) part += a_val(blk, row, 32 * kb + j) * b_val(blk, 32 * kb + j, r);
+      ref += part << (scale_exp(1, row, kb, 0) + scale_exp(1, r, kb, 1));
+    }
+    bad += acc[reg] != static_cast<float>(ref);
+  }
+  return bad;
+}
+
+__device__ __forceinline__ uint32_t check_valu(int lane, const uint32_t* __restrict__ expect, bool inject) {
+  valu_state s = valu_init(lane);
+  if (inject && lane == 0) s.x ^= 1u;
+  for (int r = 0; r < kValuRounds; ++r) {
+    valu_round(s, lane, r);
+    valu_fold(s, __shfl_xor(s.x, 1 << (r % 6), kWave));
+  }
+  return valu_digest(s) != expect[lane];
+}
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+  return v;  // lane 0 holds the sum
+}
+
+// counters[0] = waves that moved, counters[1] = their wrong results.  Waves with global
+// index < inject_waves perturb one operand of check `inject_check` (verifier self-test).
+// The dynamic LDS allocation is not used: its size keeps one workgroup per CU.
+__global__ void __launch_bounds__(256) site_probe(int ksteps, int inject_check, int inject_waves, uint32_t seed,
+                                                  const uint32_t* __restrict__ expect,
+                                                  amdgpu_canary_site_slot* __restrict__ table,
+                                                  unsigned int* __restrict__ counters,
+                                                  unsigned int* __restrict__ wave_site, int wave_site_len) {
+  const uint32_t site = site_id();
+  const int lane = threadIdx.x & (kWave - 1);
+  const uint32_t gw = blockIdx.x * kProbeWaves + (threadIdx.x >> 6);  // < 2^14 (host-checked)
+  const uint32_t key = gw | (seed << 14);
+  const bool inject = static_cast<int>(gw) < inject_waves;
+  uint32_t bad[kSiteChecks];
+  bad[0] = wave_sum(check_mfma(key, lane, ksteps, inject && inject_check == 0));
+  bad[1] = wave_sum(check_lowp(key, lane, ksteps, inject && inject_check == 1));
+  bad[2] = wave_sum(check_valu(lane, expect, inject && inject_check == 2));
+  const uint32_t site_after = site_id();
+  if (lane != 0) return;
+  if (wave_site != nullptr && static_cast<int>(gw) < wave_site_len) wave_site[gw] = site;
+  if (site_after == site) {
+    amdgpu_canary_site_slot* slot = table + site;  // site < kSiteSlots by the mask in site_id()
+    atomicAdd(&slot->waves, 1u);
+    for (int c = 0; c < kSiteChecks; ++c)
+      if (bad[c]) atomicAdd(&slot->bad[c], bad[c]);
+  } else {
+    atomicAdd(&counters[0], 1u);
+    if (bad[0] + bad[1] + bad[2]) atomicAdd(&counters[1], bad[0] + bad[1] + bad[2]);
+  }
+}
+
+// One launch with the largest dynamic LDS allocation the device grants (the selection of
+// launch_lds_march in datapath.hip: 160 KB on gfx950); false on a HIP error.
+bool launch_site_probe(const hipDeviceProp_t& prop, int blocks, int ksteps, int inject_check, int inject_waves,
+                       uint32_t seed, const uint32_t* expect, amdgpu_canary_site_slot* table, unsigned int* counters,
+                       unsigned int* wave_site, int wave_site_len) {
+  size_t bytes = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor : 0;
+  if (bytes > static_cast<size_t>(kMaxLdsBytes)) bytes = kMaxLdsBytes;
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    if (attempt == 1 || bytes == 0) bytes = prop.sharedMemPerBlock;
+    bytes &= ~static_cast<size_t>(1023);
+    if (bytes == 0) return false;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(site_probe), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              static_cast<int>(bytes));
+    hipLaunchKernelGGL(site_probe, dim3(blocks), dim3(kProbeWaves * kWave), bytes, 0, ksteps, inject_check,
+                       inject_waves, seed, expect, table, counters, wave_site, wave_site_len);
+    if (hipGetLastError() == hipSuccess) return true;
+  }
+  return false;
+}
+
+// Fills the totals and the coverage counts of `r` from a host copy of the table.
+void summarize(const amdgpu_canary_site_slot* t, amdgpu_canary_sites_result* r) {
+  for (int c = 0; c < kSiteChecks; ++c) r->errors[c] = 0;
+  r->waves = 0;
+  r->cus_reached = r->simds_reached = r->n_bad = 0;
+  for (int cu = 0; cu < kSiteSlots / 4; ++cu) {
+    bool any = false;
+    for (int simd = 0; simd < 4; ++simd) {
+      const amdgpu_canary_site_slot& s = t[cu * 4 + simd];
+      if (s.waves == 0) continue;  // errors are only ever added together with a wave
+      any = true;
+      ++r->simds_reached;
+      r->waves += s.waves;
+      for (int c = 0; c < kSiteChecks; ++c) r->errors[c] += s.bad[c];
+      if (s.bad[0] | s.bad[1] | s.bad[2]) {
+        if (r->n_bad < 16) r->bad_sites[r->n_bad] = static_cast<unsigned int>(cu * 4 + simd);
+        ++r->n_bad;
+      }
+    }
+    r->cus_reached += any;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// Runs the site probe on `device`.  blocks == 0: 2 workgroups per CU, then up to 3 more
+// launches (new operands, same table) while fewer than multiProcessorCount CUs or 4 times
+// as many SIMDs have been reached; blocks > 0: one launch of that many workgroups.
+// table_out (kSiteSlots slots) and wave_site_out (the starting site of the first
+// wave_site_len waves of the first launch) may be null.  0, or -1 with `err` set.
+int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, int inject_waves,
+                        amdgpu_canary_site_slot* table_out, unsigned int* wave_site_out, int wave_site_len,
+                        amdgpu_canary_sites_result* out, char* err, int err_len) {
+  std::memset(out, 0, sizeof(*out));
+  if (blocks < 0 || blocks > kMaxBlocks || ksteps < 1 || ksteps > 64 || inject_check < -1 ||
+      inject_check >= kSiteChecks || inject_waves < 0 || wave_site_len < 0 ||
+      (wave_site_out == nullptr && wave_site_len != 0)) {
+    std::snprintf(err, err_len, "site probe: bad arguments (blocks %d <= %d, ksteps %d in 1..64, inject %d/%d)", blocks,
+                  kMaxBlocks, ksteps, inject_check, inject_waves);
+    return -1;
+  }
+  std::vector<amdgpu_canary_site_slot> own_table(table_out ? 0 : kSiteSlots);
+  amdgpu_canary_site_slot* table = table_out ? table_out : own_table.data();
+  hipDeviceProp_t prop;
+  uint32_t h_expect[kWave];
+  unsigned int h_counters[2] = {0, 0};
+  uint32_t* d_expect = nullptr;
+  amdgpu_canary_site_slot* d_table = nullptr;
+  unsigned int *d_counters = nullptr, *d_wave_site = nullptr;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  const size_t table_bytes = sizeof(amdgpu_canary_site_slot) * kSiteSlots;
+  const char* what = "";
+  valu_expected(h_expect);
+  hipError_t e = hipSetDevice(device);
+  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
+  if (e == hipSuccess) e = hipMalloc(&d_expect, sizeof(h_expect));
+  if (e == hipSuccess) e = hipMemcpy(d_expect, h_expect, sizeof(h_expect), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc(&d_table, table_bytes);
+  if (e == hipSuccess) e = hipMemset(d_table, 0, table_bytes);
+  if (e == hipSuccess) e = hipMalloc(&d_counters, sizeof(h_counters));
+  if (e == hipSuccess) e = hipMemset(d_counters, 0, sizeof(h_counters));
+  if (e == hipSuccess && wave_site_len > 0) {
+    e = hipMalloc(&d_wave_site, sizeof(unsigned int) * wave_site_len);
+    if (e == hipSuccess) e = hipMemset(d_wave_site, 0xFF, sizeof(unsigned int) * wave_site_len);
+  }
+  if (e == hipSuccess) e = hipEventCreate(&e0);
+  if (e == hipSuccess) e = hipEventCreate(&e1);
+  if (e == hipSuccess) {
+    out->cus_expected = prop.multiProcessorCount;
+    const bool automatic = blocks == 0;
+    int grid = automatic ? 2 * prop.multiProcessorCount : blocks;
+    if (grid > kMaxBlocks) grid = kMaxBlocks;
+    const int max_launches = automatic ? 4 : 1;
+    for (int l = 0; e == hipSuccess && l < max_launches; ++l) {
+      float ms = 0;
+      e = hipEventRecord(e0, 0);
+      if (e == hipSuccess &&
+          !launch_site_probe(prop, grid, ksteps, l == 0 ? inject_check : -1, l == 0 ? inject_waves : 0,
+                             static_cast<uint32_t>(l), d_expect, d_table, d_counters, l == 0 ? d_wave_site : nullptr,
+                             l == 0 ? wave_site_len : 0)) {
+        what = "launch: ";
+        e = hipErrorLaunchFailure;
+      }
+      if (e == hipSuccess) e = hipEventRecord(e1, 0);
+      if (e == hipSuccess) e = hipEventSynchronize(e1);
+      if (e == hipSuccess) e = hipGetLastError();
+      if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
+      if (e == hipSuccess) e = hipMemcpy(table, d_table, table_bytes, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) break;
+      out->ms += ms;
+      out->launches = l + 1;
+      summarize(table, out);
+      if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected) break;
+    }
+  }
+  if (e == hipSuccess) e = hipMemcpy(h_counters, d_counters, sizeof(h_counters), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && wave_site_len > 0)
+    e = hipMemcpy(wave_site_out, d_wave_site, sizeof(unsigned int) * wave_site_len, hipMemcpyDeviceToHost);
+  out->moved = h_counters[0];
+  out->unlocated_errors = h_counters[1];
+  if (e != hipSuccess) std::snprintf(err, err_len, "site probe: %s%s", what, hipGetErrorString(e));
+  if (e0) (void)hipEventDestroy(e0);
+  if (e1) (void)hipEventDestroy(e1);
+  if (d_wave_site) (void)hipFree(d_wave_site);
+  if (d_counters) (void)hipFree(d_counters);
+  if (d_table) (void)hipFree(d_table);
+  if (d_expect) (void)hipFree(d_expect);
+  return e == hipSuccess ? 0 : -1;
+}
+
+// "xcc3/se1/sh0/cu7/simd2" of a packed site
+int amdgpu_canary_format_site(unsigned int site, char* buf, int len) {
+  return std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u/simd%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
+                       (site >> 2) & 0xFu, site & 3u);
+}
+
+}  // extern "C"
