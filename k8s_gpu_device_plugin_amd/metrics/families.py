@@ -134,7 +134,10 @@ FAMILIES = (
            "1 if the last canary run passed (exact results and the configured performance floors)"),
     Family("amdgpu_canary_errors", "gauge", ("gpu", "partition", "check"), "manager",
            "Mismatches found by the last run: hbm, mfma, gemm, lowp (fp8/bf8/fp4 MFMA), lds, site (MFMA and vector-ALU "
-           "checks of the per-CU/SIMD site probe); unreached = CUs the site probe ran on none of (not a failure)"),
+           "checks of the per-CU/SIMD site probe); unreached = CUs the site probe ran on none of (not a failure); l2 "
+           "(wrong words of the per-XCD L2 march), xcd (wrong words of the cross-XCD exchange), atomic (wrong elements "
+           "of the global-atomic tables); xcd_unreached = (writer, reader) XCD pairs the exchange did not cover (not "
+           "a failure)"),
     Family("amdgpu_canary_hbm_gbps", "gauge", ("gpu", "partition", "direction"), "manager",
            "HBM bandwidth of the last run: write, read (read + verify)"),
     Family("amdgpu_canary_matrix_tflops", "gauge", ("gpu", "partition", "path"), "manager",

@@ -21,6 +21,8 @@
 //   5. fp8 / bf8 / fp4 MFMA exactness and rate, LDS march (datapath.hip).
 //   6. Site probe        - MFMA and vector-ALU exactness on every CU and SIMD, with the
 //      place of each mismatch (sites.hip).
+//   7. Fabric check      - a march through each XCD's L2, a cross-XCD exchange and the
+//      global atomics, errors attributed per xcc and per (writer, reader) pair (fabric.hip).
 //
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
 #include <hip/hip_runtime.h>
@@ -835,6 +837,14 @@ struct amdgpu_canary_result {
   double site_ms;                       // device time of the site probe's launches
   int n_bad_sites;                      // sites with a wrong result
   unsigned int bad_sites[16];           // the first 16 of them, packed (canary_common.h)
+  unsigned long long l2_errors;         // fabric check (fabric.hip): wrong words of the L2 march, unlocated included
+  unsigned long long xcd_errors;        // wrong words of the cross-XCD exchange
+  unsigned long long atomic_errors;     // wrong elements of the global-atomic tables
+  double l2_gbps;                       // bytes the march read back / its device time (a lower bound)
+  double fabric_ms;                     // device time of the fabric check's three launches
+  int xccs_reached;                     // XCDs the march ran on
+  int xcd_pairs_reached;                // (writer, reader) XCD pairs the exchange covered
+  int xcd_pairs_unreached;              // xccs_reached^2 - pairs reached: reported, does not fail the run
 };
 
 struct amdgpu_canary_datapath_result {  // datapath.hip
@@ -976,8 +986,29 @@ int amdgpu_canary_run(int device, unsigned long long hbm_bytes, int passes, int 
                       sr.n_bad > 2 ? "s" : "");
     }
   }
+  // between a CU and HBM: each XCD's L2, the path from one XCD to another, the global atomics
+  {
+    amdgpu_canary_xcc_slot xt[kFabricXccs];
+    amdgpu_canary_pair_slot pm[kFabricXccs * kFabricXccs];
+    amdgpu_canary_fabric_result fr;
+    char ferr[256] = "";
+    if (amdgpu_canary_fabric(device, 0, 64, 2, -1, 0, 0, xt, pm, nullptr, 0, &fr, ferr, sizeof(ferr)) != 0) {
+      std::snprintf(out->error, sizeof(out->error), "%s", ferr);
+      goto done;
+    }
+    out->l2_errors = fr.l2_errors;
+    out->xcd_errors = fr.xcd_errors;
+    out->atomic_errors = fr.atomic_errors;
+    out->l2_gbps = fr.march_ms > 0 ? static_cast<double>(fr.march_read_bytes) / (fr.march_ms * 1e-3) / 1e9 : 0.0;
+    out->fabric_ms = fr.march_ms + fr.exchange_ms + fr.atomic_ms;
+    out->xccs_reached = fr.xccs_reached;
+    out->xcd_pairs_reached = fr.pairs_reached;
+    out->xcd_pairs_unreached = fr.pairs_expected > fr.pairs_reached ? fr.pairs_expected - fr.pairs_reached : 0;
+    if (out->error[0] == 0) amdgpu_canary_fabric_describe(&fr, xt, pm, out->error, sizeof(out->error));
+  }
   out->ok = (out->hbm_errors == 0 && out->mfma_errors == 0 && out->gemm_errors == 0 && out->lowp_errors == 0 &&
-             out->lds_errors == 0 && out->site_errors == 0)
+             out->lds_errors == 0 && out->site_errors == 0 && out->l2_errors == 0 && out->xcd_errors == 0 &&
+             out->atomic_errors == 0)
                 ? 1
                 : 0;
 done:

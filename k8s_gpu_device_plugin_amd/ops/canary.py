@@ -3,14 +3,16 @@
 ``run(device)`` loads ``libamdgpu_canary.so`` with ctypes (no torch needed) and runs
 the HBM pattern test, the MFMA exactness/throughput probe, the matrix-path check
 (an LDS-staged MFMA GEMM on exact integer data with ABFT row/column checksums), the
-fp8 / bf8 / fp4 MFMA exactness and rate checks, the LDS march (``datapath.hip``) and the
+fp8 / bf8 / fp4 MFMA exactness and rate checks, the LDS march (``datapath.hip``), the
 site probe (``sites.hip``: MFMA and vector-ALU exactness on every CU and SIMD, each
-mismatch located) on
+mismatch located) and the fabric check (``fabric.hip``: a march through each XCD's L2, a
+cross-XCD exchange and the global atomics) on
 one HIP device (= one compute partition).  ``run_isolated(device)`` does the same in a child process so the
 long-lived plugin daemon never creates a HIP context on GPUs it hands to pods.
 
 CLI: ``python -m k8s_gpu_device_plugin_amd.ops.canary --device 0 [--bytes N]`` prints
-one JSON line; ``--sites`` prints the site probe's coverage map instead.  Missing library => loud ``RuntimeError`` (never a silent pass).
+one JSON line; ``--sites`` prints the site probe's coverage map instead, ``--fabric`` the
+fabric check's per-XCD tables.  Missing library => loud ``RuntimeError`` (never a silent pass).
 """
 from __future__ import annotations
 
@@ -35,7 +37,11 @@ class CanaryResult(ctypes.Structure):
                 ("lds_errors", ctypes.c_ulonglong), ("lds_bytes", ctypes.c_ulonglong),
                 ("site_errors", ctypes.c_ulonglong), ("cus_reached", ctypes.c_int),
                 ("simds_reached", ctypes.c_int), ("cus_unreached", ctypes.c_int), ("site_ms", ctypes.c_double),
-                ("n_bad_sites", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16)]
+                ("n_bad_sites", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16),
+                ("l2_errors", ctypes.c_ulonglong), ("xcd_errors", ctypes.c_ulonglong),
+                ("atomic_errors", ctypes.c_ulonglong), ("l2_gbps", ctypes.c_double), ("fabric_ms", ctypes.c_double),
+                ("xccs_reached", ctypes.c_int), ("xcd_pairs_reached", ctypes.c_int),
+                ("xcd_pairs_unreached", ctypes.c_int)]
 
 
 SITE_SLOTS = 1 << 14
@@ -51,6 +57,37 @@ class SitesResult(ctypes.Structure):
                 ("waves", ctypes.c_ulonglong), ("moved", ctypes.c_ulonglong), ("launches", ctypes.c_int),
                 ("cus_reached", ctypes.c_int), ("simds_reached", ctypes.c_int), ("cus_expected", ctypes.c_int),
                 ("n_bad", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16), ("ms", ctypes.c_double)]
+
+
+FABRIC_XCCS = 16
+# the global-atomic forms of the fabric check, in the order of ops/fabric.hip
+ATOMIC_OPS = ("u32_add", "u64_add", "i32_min", "u32_max", "u64_max", "and", "or", "xor", "f32_add", "f64_add",
+              "pk_add_bf16", "pk_add_f16", "cas_inc", "ticket")
+FABRIC_INJECT = ("l2", "xcd", "atomic")
+ATOMIC_ELEMS = 2048
+# element type of each operation's table: the packed forms as 16-bit patterns (low half first),
+# cas_inc as its 64 words, ticket as the ticket word followed by seen[16384]
+_ATOMIC_DTYPES = {"u64_add": "uint64", "u64_max": "uint64", "i32_min": "int32", "f32_add": "float32",
+                  "f64_add": "float64", "pk_add_bf16": "uint16", "pk_add_f16": "uint16"}
+
+
+class XccSlot(ctypes.Structure):
+    _fields_ = [("blocks", ctypes.c_ulonglong), ("bytes", ctypes.c_ulonglong), ("bad", ctypes.c_ulonglong)]
+
+
+class PairSlot(ctypes.Structure):
+    _fields_ = [("reads", ctypes.c_ulonglong), ("bad", ctypes.c_ulonglong)]
+
+
+class FabricResult(ctypes.Structure):
+    _fields_ = [("l2_errors", ctypes.c_ulonglong), ("unlocated_errors", ctypes.c_ulonglong),
+                ("xcd_errors", ctypes.c_ulonglong), ("atomic_errors", ctypes.c_ulonglong),
+                ("moved", ctypes.c_ulonglong), ("atomic_bad", ctypes.c_ulonglong * len(ATOMIC_OPS)),
+                ("march_read_bytes", ctypes.c_ulonglong), ("blocks", ctypes.c_int), ("slice_kb", ctypes.c_int),
+                ("xccs_reached", ctypes.c_int), ("pairs_reached", ctypes.c_int), ("pairs_expected", ctypes.c_int),
+                ("first_bad_slice", ctypes.c_int), ("first_bad_offset", ctypes.c_uint),
+                ("first_bad_xcc", ctypes.c_int), ("first_bad_op", ctypes.c_int), ("first_bad_elem", ctypes.c_int),
+                ("march_ms", ctypes.c_double), ("exchange_ms", ctypes.c_double), ("atomic_ms", ctypes.c_double)]
 
 
 def decode_site(packed: int) -> dict:
@@ -114,6 +151,16 @@ def load():
                                                                  ctypes.POINTER(SitesResult), ctypes.c_char_p,
                                                                  ctypes.c_int]
         lib.amdgpu_canary_sites.restype = ctypes.c_int
+        lib.amdgpu_canary_fabric.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(XccSlot), ctypes.POINTER(PairSlot),
+                                                                  ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
+                                                                  ctypes.POINTER(FabricResult), ctypes.c_char_p,
+                                                                  ctypes.c_int]
+        lib.amdgpu_canary_fabric.restype = ctypes.c_int
+        lib.amdgpu_canary_fabric_describe.argtypes = [ctypes.POINTER(FabricResult), ctypes.POINTER(XccSlot),
+                                                      ctypes.POINTER(PairSlot), ctypes.c_char_p, ctypes.c_int]
+        lib.amdgpu_canary_fabric_describe.restype = ctypes.c_int
+        lib.amdgpu_canary_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+        lib.amdgpu_canary_atomic_expected.restype = ctypes.c_int
         _lib = lib
     return _lib
 
@@ -162,6 +209,71 @@ def site_probe(device: int = 0, blocks: int = 0, ksteps: int = 4, inject=None, i
                     for p, s in enumerate(table) if s.waves}
     out["wave_sites"] = [format_site(p) for p in wave_sites if p != 0xFFFFFFFF]  # unwritten entries stay all-ones
     return out
+
+
+def fabric_check(device: int = 0, blocks: int = 0, slice_kb: int = 64, reps: int = 2, inject=None,
+                 inject_op: str = "u32_add", inject_blocks: int = 0) -> dict:
+    """What lies between a CU and HBM (``ops/fabric.hip``), in three launches of ``blocks``
+    256-thread workgroups (0: one per CU).  The L2 march: each workgroup writes a slice of
+    ``slice_kb`` KiB, reads it back ``reps`` times while it is resident in its XCD's L2, then
+    does the same with the complement.  The exchange: every slice is verified again by a
+    later launch, per (writer xcc, reader xcc).  The atomics: every global atomic form into
+    tables the host predicts.  ``inject`` (``l2``, ``xcd`` or ``atomic``, the latter in
+    operation ``inject_op``) makes the first ``inject_blocks`` workgroups plant a fault.
+
+    Returns the totals (``l2_errors``, ``xcd_errors``, ``atomic_errors``, ``unlocated_errors``,
+    ``moved``), ``xccs`` (``"xcc5"`` -> blocks, bytes, bad), ``pairs`` (``"xcc1>xcc6"``: written
+    on xcc1, read on xcc6 -> reads, bad), ``slice_xcc`` (the xcc that wrote each slice),
+    ``atomic`` (operation -> wrong elements), ``first_bad`` (``l2``: xcc, slice, offset;
+    ``atomic``: op, element), ``error`` (the canary's text for the first failing check),
+    ``l2_gbps`` (bytes the march read back over the march's whole device time: a lower
+    bound) and ``ms``."""
+    kind = -1 if inject is None else FABRIC_INJECT.index(inject)
+    lib = load()
+    r = FabricResult()
+    xt = (XccSlot * FABRIC_XCCS)()
+    pm = (PairSlot * (FABRIC_XCCS * FABRIC_XCCS))()
+    n_slices = int(blocks) if blocks > 0 else 4096
+    sx = (ctypes.c_uint * n_slices)()
+    err = ctypes.create_string_buffer(256)
+    rc = lib.amdgpu_canary_fabric(int(device), int(blocks), int(slice_kb), int(reps), kind,
+                                  ATOMIC_OPS.index(inject_op), int(inject_blocks), xt, pm, sx, n_slices,
+                                  ctypes.byref(r), err, 256)
+    if rc != 0:
+        raise RuntimeError("fabric_check failed: " + err.value.decode(errors="replace"))
+    out = {f: int(getattr(r, f)) for f in ("l2_errors", "xcd_errors", "atomic_errors", "unlocated_errors", "moved",
+                                           "blocks", "slice_kb", "xccs_reached", "pairs_reached", "pairs_expected")}
+    out["xccs"] = {"xcc%d" % x: {"blocks": int(s.blocks), "bytes": int(s.bytes), "bad": int(s.bad)}
+                   for x, s in enumerate(xt) if s.blocks}
+    out["pairs"] = {"xcc%d>xcc%d" % divmod(c, FABRIC_XCCS): {"reads": int(p.reads), "bad": int(p.bad)}
+                    for c, p in enumerate(pm) if p.reads}
+    out["slice_xcc"] = [int(x) for x in sx[:r.blocks]]
+    out["atomic"] = {op: int(r.atomic_bad[i]) for i, op in enumerate(ATOMIC_OPS)}
+    out["first_bad"] = {
+        "l2": None if r.first_bad_slice < 0 else {"xcc": r.first_bad_xcc, "slice": r.first_bad_slice,
+                                                  "offset": int(r.first_bad_offset)},
+        "atomic": None if r.first_bad_op < 0 else {"op": ATOMIC_OPS[r.first_bad_op], "element": r.first_bad_elem}}
+    lib.amdgpu_canary_fabric_describe(ctypes.byref(r), xt, pm, err, 256)
+    out["error"] = err.value.decode(errors="replace") if out["l2_errors"] or out["xcd_errors"] or \
+        out["atomic_errors"] else ""
+    out["l2_gbps"] = r.march_read_bytes / (r.march_ms * 1e-3) / 1e9 if r.march_ms > 0 else 0.0
+    out["march_ms"], out["exchange_ms"], out["atomic_ms"] = r.march_ms, r.exchange_ms, r.atomic_ms
+    out["ms"] = r.march_ms + r.exchange_ms + r.atomic_ms
+    return out
+
+
+def atomic_expected(op: str, blocks: int):
+    """The table operation ``op`` (one of ``ATOMIC_OPS``) must hold after the fabric check's
+    atomics ran as ``blocks`` workgroups, computed on the host (no GPU needed): a numpy array
+    of 2048 elements (4096 16-bit patterns for the packed forms, low half first), the 64
+    words of ``cas_inc``, or the ticket word followed by ``seen[16384]`` for ``ticket``."""
+    import numpy as np
+
+    buf = np.zeros(1 + 16384, dtype=np.uint32)
+    n = load().amdgpu_canary_atomic_expected(ATOMIC_OPS.index(op), int(blocks), buf.ctypes.data, buf.nbytes)
+    if n < 0:
+        raise ValueError("atomic_expected(%s, %r): blocks must be in 1..4096" % (op, blocks))
+    return buf.view(np.uint8)[:n].view(_ATOMIC_DTYPES.get(op, "uint32")).copy()
 
 
 def detects_corruption(device: int = 0, hbm_bytes: int = 64 << 20, flips: int = 5) -> int:
@@ -352,7 +464,13 @@ def main(argv=None) -> int:
     ap.add_argument("--gemm-kernel", choices=sorted(GEMM_KERNELS), default="auto")
     ap.add_argument("--gemm-random", action="store_true", help="random bf16 operands (rate only, no checksum)")
     ap.add_argument("--sites", action="store_true", help="only the site probe: the CU/SIMD coverage map")
+    ap.add_argument("--fabric", action="store_true",
+                    help="only the fabric check: L2 march, cross-XCD exchange, global atomics")
     a = ap.parse_args(argv)
+    if a.fabric:
+        res = fabric_check(a.device)
+        print(json.dumps(res))
+        return 0 if not (res["l2_errors"] or res["xcd_errors"] or res["atomic_errors"]) else 1
     if a.sites:
         res = site_probe(a.device)
         print(json.dumps(res))

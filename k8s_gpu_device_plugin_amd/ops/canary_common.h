@@ -1,6 +1,7 @@
-// Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip, sites.hip): the
-// hash that derives exact small-integer operands, the MFMA register vector types, the
-// bf16 / OCP low-precision operand packing, and the site probe's C ABI.
+// Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip, sites.hip,
+// fabric.hip): the hash that derives exact small-integer operands, the MFMA register vector
+// types, the bf16 / OCP low-precision operand packing, the s_getreg immediates, and the C
+// ABI of the site probe and the fabric check.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,10 @@ namespace canary {
 constexpr int kWave = 64;
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// s_getreg_b32 immediate: register id 5:0, bit offset 10:6, size - 1 15:11
+constexpr int kHwRegHwId = 4, kHwRegXccId = 20;
+constexpr int getreg_imm(int reg, int offset, int size) { return ((size - 1) << 11) | (offset << 6) | reg; }
 
 __device__ __forceinline__ uint32_t mix32(uint64_t x) {
   x ^= x >> 33;
@@ -117,5 +122,54 @@ int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, in
                         amdgpu_canary_site_slot* table_out, unsigned int* wave_site_out, int wave_site_len,
                         amdgpu_canary_sites_result* result, char* err, int err_len);
 int amdgpu_canary_format_site(unsigned int site, char* buf, int len);  // "xcc3/se1/sh0/cu7/simd2"
+
+// ---- fabric check (fabric.hip): per-XCD L2 march, cross-XCD exchange, global atomics ----
+constexpr int kFabricXccs = 16;    // HW_REG_XCC_ID is 4 bits wide
+constexpr int kAtomicOps = 14;     // order of canary.ATOMIC_OPS
+constexpr int kAtomicElems = 2048; // elements of one operation's table
+
+struct amdgpu_canary_xcc_slot {  // one per xcc: what the L2 march did there
+  unsigned long long blocks;     // workgroups (= slices) that ran on it from first to last
+  unsigned long long bytes;      // bytes of their slices
+  unsigned long long bad;        // wrong 32-bit words they read back
+};
+
+struct amdgpu_canary_pair_slot {  // matrix[writer xcc][reader xcc] of the exchange
+  unsigned long long reads;       // slices read
+  unsigned long long bad;         // wrong 32-bit words in them
+};
+
+struct amdgpu_canary_fabric_result {
+  unsigned long long l2_errors;         // wrong words of the march, unlocated ones included
+  unsigned long long unlocated_errors;  // those of workgroups whose xcc changed while they ran
+  unsigned long long xcd_errors;        // wrong words of the exchange
+  unsigned long long atomic_errors;     // wrong table elements over all operations
+  unsigned long long moved;             // workgroups (of either launch) whose xcc changed
+  unsigned long long atomic_bad[kAtomicOps];
+  unsigned long long march_read_bytes;  // bytes the march's read passes loaded
+  int blocks;                           // the grid of all three launches
+  int slice_kb;
+  int xccs_reached;                     // xccs with a located march workgroup
+  int pairs_reached;                    // non-empty cells of the pair matrix
+  int pairs_expected;                   // xccs_reached squared
+  int first_bad_slice;                  // first wrong word of the march: slice (-1: none),
+  unsigned int first_bad_offset;        //   byte offset in it,
+  int first_bad_xcc;                    //   and the xcc its workgroup started on
+  int first_bad_op;                     // first wrong atomic element: operation (-1: none)
+  int first_bad_elem;
+  double march_ms;                      // device time of each launch
+  double exchange_ms;
+  double atomic_ms;
+};
+
+int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inject_kind, int inject_op,
+                         int inject_blocks, amdgpu_canary_xcc_slot* xcc_table_out,
+                         amdgpu_canary_pair_slot* pair_matrix_out, unsigned int* slice_xcc_out, int slice_xcc_len,
+                         amdgpu_canary_fabric_result* result, char* err, int err_len);
+int amdgpu_canary_atomic_expected(int op, int blocks, void* out, int out_bytes);
+const char* amdgpu_canary_atomic_op_name(int op);  // "u64 add"
+// "l2 check: 3 wrong words on xcc5 (slice 17, offset 0x1a40)" of the first failing check; 0 if none failed
+int amdgpu_canary_fabric_describe(const amdgpu_canary_fabric_result* r, const amdgpu_canary_xcc_slot* xcc_table,
+                                  const amdgpu_canary_pair_slot* pair_matrix, char* buf, int len);
 
 }  // extern "C"

@@ -43,10 +43,6 @@ constexpr int kMaxBlocks = 4096; // global wave index < 2^14
 constexpr int kMaxLdsBytes = 160 * 1024;
 constexpr int kValuRounds = 48;
 
-// s_getreg_b32 immediate: register id 5:0, bit offset 10:6, size - 1 15:11
-constexpr int kHwRegHwId = 4, kHwRegXccId = 20;
-constexpr int getreg_imm(int reg, int offset, int size) { return ((size - 1) << 11) | (offset << 6) | reg; }
-
 // HW_ID 15:4 = simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (3 bits: 14:13 on gfx942/950,
 // bit 15 reads 0 there).  cu, sh and se are contiguous, so they move as one 8-bit field.
 __device__ __forceinline__ uint32_t site_id() {

@@ -1604,7 +1604,8 @@ class PluginManager:
             rows["amdgpu_canary_last_ok"].append("{%s} %d" % (lab, int(bool(r.get("ok")))))
             for check, key in (("hbm", "hbm_errors"), ("mfma", "mfma_errors"), ("gemm", "gemm_errors"),
                                ("lowp", "lowp_errors"), ("lds", "lds_errors"), ("site", "site_errors"),
-                               ("unreached", "cus_unreached")):
+                               ("unreached", "cus_unreached"), ("l2", "l2_errors"), ("xcd", "xcd_errors"),
+                               ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached")):
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
