@@ -137,7 +137,8 @@ FAMILIES = (
            "checks of the per-CU/SIMD site probe); unreached = CUs the site probe ran on none of (not a failure); l2 "
            "(wrong words of the per-XCD L2 march), xcd (wrong words of the cross-XCD exchange), atomic (wrong elements "
            "of the global-atomic tables); xcd_unreached = (writer, reader) XCD pairs the exchange did not cover (not "
-           "a failure)"),
+           "a failure); reg (wrong words of the vector register file march, VGPRs and AGPRs), l1 (wrong words "
+           "re-read through a CU's vector L1)"),
     Family("amdgpu_canary_hbm_gbps", "gauge", ("gpu", "partition", "direction"), "manager",
            "HBM bandwidth of the last run: write, read (read + verify)"),
     Family("amdgpu_canary_matrix_tflops", "gauge", ("gpu", "partition", "path"), "manager",

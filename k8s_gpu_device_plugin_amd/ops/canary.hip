@@ -23,6 +23,9 @@
 //      place of each mismatch (sites.hip).
 //   7. Fabric check      - a march through each XCD's L2, a cross-XCD exchange and the
 //      global atomics, errors attributed per xcc and per (writer, reader) pair (fabric.hip).
+//   8. CU memory check   - a march over each SIMD's vector register file (VGPRs and AGPRs)
+//      and re-reads through each CU's vector L1, located per SIMD / CU (cumem.hip).  Not part
+//      of amdgpu_canary_run: canary.py's run() calls amdgpu_canary_cu and merges its result.
 //
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
 #include <hip/hip_runtime.h>

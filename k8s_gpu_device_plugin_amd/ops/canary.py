@@ -5,14 +5,16 @@ the HBM pattern test, the MFMA exactness/throughput probe, the matrix-path check
 (an LDS-staged MFMA GEMM on exact integer data with ABFT row/column checksums), the
 fp8 / bf8 / fp4 MFMA exactness and rate checks, the LDS march (``datapath.hip``), the
 site probe (``sites.hip``: MFMA and vector-ALU exactness on every CU and SIMD, each
-mismatch located) and the fabric check (``fabric.hip``: a march through each XCD's L2, a
-cross-XCD exchange and the global atomics) on
+mismatch located), the fabric check (``fabric.hip``: a march through each XCD's L2, a
+cross-XCD exchange and the global atomics) and the CU memory check (``cumem.hip``: a march
+over each SIMD's vector register file and re-reads through each CU's vector L1) on
 one HIP device (= one compute partition).  ``run_isolated(device)`` does the same in a child process so the
 long-lived plugin daemon never creates a HIP context on GPUs it hands to pods.
 
 CLI: ``python -m k8s_gpu_device_plugin_amd.ops.canary --device 0 [--bytes N]`` prints
 one JSON line; ``--sites`` prints the site probe's coverage map instead, ``--fabric`` the
-fabric check's per-XCD tables.  Missing library => loud ``RuntimeError`` (never a silent pass).
+fabric check's per-XCD tables, ``--cu`` the CU memory check's per-site table.  Missing
+library => loud ``RuntimeError`` (never a silent pass).
 """
 from __future__ import annotations
 
@@ -90,6 +92,25 @@ class FabricResult(ctypes.Structure):
                 ("march_ms", ctypes.c_double), ("exchange_ms", ctypes.c_double), ("atomic_ms", ctypes.c_double)]
 
 
+CU_INJECT = ("vgpr", "agpr", "l1")
+
+
+class CuSlot(ctypes.Structure):
+    _fields_ = [("waves", ctypes.c_uint), ("bad_vgpr", ctypes.c_uint), ("bad_agpr", ctypes.c_uint),
+                ("bad_l1", ctypes.c_uint)]
+
+
+class CuResult(ctypes.Structure):
+    _fields_ = [("vgpr_errors", ctypes.c_ulonglong), ("agpr_errors", ctypes.c_ulonglong),
+                ("l1_errors", ctypes.c_ulonglong), ("l1_fill_errors", ctypes.c_ulonglong),
+                ("unlocated_errors", ctypes.c_ulonglong), ("moved", ctypes.c_ulonglong),
+                ("waves", ctypes.c_ulonglong), ("l1_moved", ctypes.c_ulonglong), ("launches", ctypes.c_int),
+                ("cus_reached", ctypes.c_int), ("simds_reached", ctypes.c_int), ("cus_expected", ctypes.c_int),
+                ("l1_cus_reached", ctypes.c_int), ("regs_vgpr", ctypes.c_int), ("regs_agpr", ctypes.c_int),
+                ("n_bad", ctypes.c_int), ("bad_sites", ctypes.c_uint * 16), ("reg_ms", ctypes.c_double),
+                ("l1_ms", ctypes.c_double)]
+
+
 def decode_site(packed: int) -> dict:
     """Fields of a packed site: simd bits 1:0, cu 5:2, sh 6, se 9:7, xcc 13:10 (the layout
     ``site_id()`` in ``ops/sites.hip`` builds from HW_REG_HW_ID and HW_REG_XCC_ID)."""
@@ -161,6 +182,17 @@ def load():
         lib.amdgpu_canary_fabric_describe.restype = ctypes.c_int
         lib.amdgpu_canary_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
         lib.amdgpu_canary_atomic_expected.restype = ctypes.c_int
+        lib.amdgpu_canary_cu.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(CuSlot), ctypes.POINTER(ctypes.c_uint),
+                                                              ctypes.c_int, ctypes.POINTER(CuResult),
+                                                              ctypes.c_char_p, ctypes.c_int]
+        lib.amdgpu_canary_cu.restype = ctypes.c_int
+        lib.amdgpu_canary_cu_describe.argtypes = [ctypes.POINTER(CuResult), ctypes.POINTER(CuSlot), ctypes.c_char_p,
+                                                  ctypes.c_int]
+        lib.amdgpu_canary_cu_describe.restype = ctypes.c_int
+        lib.amdgpu_canary_cu_regs.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+        lib.amdgpu_canary_cu_regs.restype = None
+        lib.amdgpu_canary_cu_sizeof.argtypes = [ctypes.c_int]
+        lib.amdgpu_canary_cu_sizeof.restype = ctypes.c_int
         _lib = lib
     return _lib
 
@@ -177,6 +209,72 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     out["error"] = r.error.decode(errors="replace")
     out["ok"] = bool(r.ok) and rc == 0
     out["bad_sites"] = [format_site(p) for p in r.bad_sites[:min(r.n_bad_sites, 16)]]
+    # the CU memory check has its own entry point (amdgpu_canary_result is a fixed ABI):
+    # same process, same device, merged into the same verdict
+    try:
+        cu = cu_check(device)
+    except (RuntimeError, OSError) as e:
+        out["ok"] = False
+        out["error"] = out["error"] or str(e)
+        return out
+    out["reg_errors"] = cu["vgpr_errors"] + cu["agpr_errors"] + cu["unlocated_errors"]
+    out["l1_errors"] = cu["l1_errors"]
+    out["l1_fill_errors"] = cu["l1_fill_errors"]  # came from L2 / HBM: reported, not an L1 verdict
+    out["cu_ms"] = cu["reg_ms"] + cu["l1_ms"]
+    out["regs_marched"] = cu["regs_marched"]
+    out["cu_bad_sites"] = cu["bad_sites"]
+    if out["reg_errors"] or out["l1_errors"]:
+        out["ok"] = False
+        out["error"] = out["error"] or cu["error"]
+    return out
+
+
+def cu_check(device: int = 0, blocks: int = 0, reps: int = 2, l1_kb: int = 16, l1_reps: int = 4, inject=None,
+             inject_waves: int = 0) -> dict:
+    """The two storage arrays next to the ALUs (``ops/cumem.hip``), as 4-wave workgroups whose
+    waves record their site like the site probe's.  The register march: every lane keeps
+    ``regs_vgpr`` values pinned in VGPRs and ``regs_agpr`` in AGPRs, all live at once (a wave
+    is allocated its SIMD's whole 512-entry file), writes them, verifies them ascending, writes
+    the complement and verifies descending, ``reps`` times.  The L1 march: each workgroup (one
+    resident per CU) reads its ``l1_kb`` KiB slice with plain loads, then re-reads it
+    ``l1_reps`` times, alternately reversed and forward.  ``blocks=0``: 2 workgroups per CU
+    plus up to 3 top-up launches while a CU or SIMD is missing; ``blocks>0``: one launch.
+    ``inject`` (``vgpr``, ``agpr`` or ``l1``) makes the first ``inject_waves`` waves (``l1``:
+    workgroups) flip one bit of one value they then compare.
+
+    Returns the totals (``vgpr_errors``, ``agpr_errors``, ``unlocated_errors``: wrong register
+    words; ``l1_errors``: wrong re-read words; ``l1_fill_errors``: wrong words of the first
+    read, which came from L2 or HBM), the coverage counts, ``regs_marched`` and
+    ``reg_bytes_per_simd``, ``sites``, ``wave_sites`` / ``l1_wave_sites`` (the site of each
+    wave of the first launch of either kernel), ``bad_sites`` and ``error`` (the canary's
+    text for the first failing check)."""
+    kind = -1 if inject is None else CU_INJECT.index(inject)
+    lib = load()
+    r = CuResult()
+    table = (CuSlot * SITE_SLOTS)()
+    n_waves = 4 * (int(blocks) if blocks > 0 else 2 * 1024)  # automatic: room for 1024 CUs
+    wave_sites = (ctypes.c_uint * (2 * n_waves))()  # the register march's, then the L1 march's
+    err = ctypes.create_string_buffer(256)
+    rc = lib.amdgpu_canary_cu(int(device), int(blocks), int(reps), int(l1_kb), int(l1_reps), kind, int(inject_waves),
+                              table, wave_sites, n_waves, ctypes.byref(r), err, 256)
+    if rc != 0:
+        raise RuntimeError("cu_check failed: " + err.value.decode(errors="replace"))
+    out = {f: int(getattr(r, f)) for f in ("vgpr_errors", "agpr_errors", "l1_errors", "l1_fill_errors",
+                                           "unlocated_errors", "moved", "waves", "l1_moved", "launches",
+                                           "cus_reached", "simds_reached", "cus_expected", "l1_cus_reached",
+                                           "regs_vgpr", "regs_agpr", "n_bad")}
+    out["regs_marched"] = out["regs_vgpr"] + out["regs_agpr"]
+    out["reg_bytes_per_simd"] = out["regs_marched"] * 256  # 64 lanes x 4 B per entry
+    out["reg_ms"], out["l1_ms"] = r.reg_ms, r.l1_ms
+    out["bad_sites"] = [format_site(p) for p in r.bad_sites[:min(r.n_bad, 16)]]
+    out["sites"] = {format_site(p): {"waves": int(s.waves), "vgpr": int(s.bad_vgpr), "agpr": int(s.bad_agpr),
+                                     "l1": int(s.bad_l1)}
+                    for p, s in enumerate(table) if s.waves or s.bad_l1}
+    out["wave_sites"] = [format_site(p) for p in wave_sites[:n_waves] if p != 0xFFFFFFFF]  # unwritten: all-ones
+    out["l1_wave_sites"] = [format_site(p) for p in wave_sites[n_waves:] if p != 0xFFFFFFFF]
+    lib.amdgpu_canary_cu_describe(ctypes.byref(r), table, err, 256)
+    out["error"] = err.value.decode(errors="replace") if out["vgpr_errors"] or out["agpr_errors"] or \
+        out["unlocated_errors"] or out["l1_errors"] else ""
     return out
 
 
@@ -466,7 +564,14 @@ def main(argv=None) -> int:
     ap.add_argument("--sites", action="store_true", help="only the site probe: the CU/SIMD coverage map")
     ap.add_argument("--fabric", action="store_true",
                     help="only the fabric check: L2 march, cross-XCD exchange, global atomics")
+    ap.add_argument("--cu", action="store_true",
+                    help="only the CU memory check: register-file march and L1 march, per site")
     a = ap.parse_args(argv)
+    if a.cu:
+        res = cu_check(a.device)
+        print(json.dumps(res))
+        return 0 if not (res["vgpr_errors"] or res["agpr_errors"] or res["unlocated_errors"] or
+                         res["l1_errors"]) else 1
     if a.fabric:
         res = fabric_check(a.device)
         print(json.dumps(res))

@@ -1,7 +1,8 @@
 // Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip, sites.hip,
-// fabric.hip): the hash that derives exact small-integer operands, the MFMA register vector
-// types, the bf16 / OCP low-precision operand packing, the s_getreg immediates, and the C
-// ABI of the site probe and the fabric check.
+// fabric.hip, cumem.hip): the hash that derives exact small-integer operands, the MFMA
+// register vector types, the bf16 / OCP low-precision operand packing, the s_getreg
+// immediates, site_id(), and the C ABI of the site probe, the fabric check and the CU
+// memory check.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -94,9 +95,22 @@ __device__ __forceinline__ int scale_exp(int vary, int rc, int kb, int which) {
 // ---- site probe (sites.hip): where on the chip each exactness check ran ----------------
 // A site is (xcc, se, sh, cu, simd) packed into 14 bits:
 //   simd 1:0 | cu 5:2 | sh 6 | se 9:7 | xcc 13:10
+constexpr int kSiteSlots = 1 << 14;
+
+namespace canary {
+
+// HW_ID 15:4 = simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (3 bits: 14:13 on gfx942/950,
+// bit 15 reads 0 there).  cu, sh and se are contiguous, so they move as one 8-bit field.
+__device__ __forceinline__ uint32_t site_id() {
+  const uint32_t hw = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegHwId, 4, 12));
+  const uint32_t xcc = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegXccId, 0, 4));
+  return ((hw & 3u) | (((hw >> 4) & 0xFFu) << 2) | ((xcc & 0xFu) << 10)) & (kSiteSlots - 1);
+}
+
+}  // namespace canary
+
 extern "C" {
 
-constexpr int kSiteSlots = 1 << 14;
 constexpr int kSiteChecks = 3;  // 0 mfma, 1 lowp, 2 valu
 
 struct amdgpu_canary_site_slot {  // one per packed site
@@ -171,5 +185,49 @@ const char* amdgpu_canary_atomic_op_name(int op);  // "u64 add"
 // "l2 check: 3 wrong words on xcc5 (slice 17, offset 0x1a40)" of the first failing check; 0 if none failed
 int amdgpu_canary_fabric_describe(const amdgpu_canary_fabric_result* r, const amdgpu_canary_xcc_slot* xcc_table,
                                   const amdgpu_canary_pair_slot* pair_matrix, char* buf, int len);
+
+// ---- CU memory check (cumem.hip): vector register file march, per-CU L1 march -----------
+constexpr int kCuInjectKinds = 3;  // 0 vgpr, 1 agpr, 2 l1
+
+struct amdgpu_canary_cu_slot {  // one per packed site
+  unsigned int waves;           // reg_march waves that ran here from first to last
+  unsigned int bad_vgpr;        // wrong words they read back from values pinned in VGPRs
+  unsigned int bad_agpr;        //   ... and in AGPRs
+  unsigned int bad_l1;          // wrong words l1_march waves here saw in a re-read pass
+};
+
+struct amdgpu_canary_cu_result {
+  unsigned long long vgpr_errors;       // located wrong words of the register march
+  unsigned long long agpr_errors;
+  unsigned long long l1_errors;         // wrong words of the re-read passes, unlocated ones included
+  unsigned long long l1_fill_errors;    // wrong words of pass 1 (from L2 / HBM: not an L1 verdict)
+  unsigned long long unlocated_errors;  // wrong register words of waves that changed site while marching
+  unsigned long long moved;             // reg_march waves that changed site
+  unsigned long long waves;             // located reg_march waves
+  unsigned long long l1_moved;          // l1_march waves that changed site (their errors stay in l1_errors)
+  int launches;
+  int cus_reached;     // distinct (xcc, se, sh, cu) with a located reg_march wave
+  int simds_reached;   // distinct sites with one
+  int cus_expected;    // multiProcessorCount
+  int l1_cus_reached;  // distinct (xcc, se, sh, cu) whose L1 a located l1_march wave re-read
+  int regs_vgpr;       // NV: values each lane keeps pinned in VGPRs
+  int regs_agpr;       // NA: ... in AGPRs
+  int n_bad;           // sites with a wrong word of any kind
+  unsigned int bad_sites[16];  // the first 16 of them, packed
+  double reg_ms;       // device time of the reg_march launches
+  double l1_ms;        // device time of l1_fill and the l1_march launches
+};
+
+// wave_site_out, when not null, holds 2 * wave_site_len entries: the starting site of the
+// first wave_site_len waves of the first reg_march launch, then those of the first l1_march.
+int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, int inject_kind, int inject_waves,
+                     amdgpu_canary_cu_slot* table_out, unsigned int* wave_site_out, int wave_site_len,
+                     amdgpu_canary_cu_result* result, char* err, int err_len);
+void amdgpu_canary_cu_regs(int* nv, int* na);
+int amdgpu_canary_cu_sizeof(int which);  // 0: amdgpu_canary_cu_slot, 1: amdgpu_canary_cu_result
+// "register check: 3 wrong words at xcc3/se1/sh0/cu7/simd2 (agpr; +1 more site)", else
+// "l1 check: 2 wrong words at xcc3/se1/sh0/cu7"; 0 if neither failed.  `table`: kSiteSlots slots.
+int amdgpu_canary_cu_describe(const amdgpu_canary_cu_result* r, const amdgpu_canary_cu_slot* table, char* buf,
+                              int len);
 
 }  // extern "C"

@@ -43,14 +43,6 @@ constexpr int kMaxBlocks = 4096; // global wave index < 2^14
 constexpr int kMaxLdsBytes = 160 * 1024;
 constexpr int kValuRounds = 48;
 
-// HW_ID 15:4 = simd 5:4, pipe 7:6, cu 11:8, sh 12, se 15:13 (3 bits: 14:13 on gfx942/950,
-// bit 15 reads 0 there).  cu, sh and se are contiguous, so they move as one 8-bit field.
-__device__ __forceinline__ uint32_t site_id() {
-  const uint32_t hw = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegHwId, 4, 12));
-  const uint32_t xcc = __builtin_amdgcn_s_getreg(getreg_imm(kHwRegXccId, 0, 4));
-  return ((hw & 3u) | (((hw >> 4) & 0xFFu) << 2) | ((xcc & 0xFu) << 10)) & (kSiteSlots - 1);
-}
-
 // ---- valu chain: the same code on host and device ----------------------------------
 struct valu_state {
   uint32_t x;

@@ -1605,7 +1605,8 @@ class PluginManager:
             for check, key in (("hbm", "hbm_errors"), ("mfma", "mfma_errors"), ("gemm", "gemm_errors"),
                                ("lowp", "lowp_errors"), ("lds", "lds_errors"), ("site", "site_errors"),
                                ("unreached", "cus_unreached"), ("l2", "l2_errors"), ("xcd", "xcd_errors"),
-                               ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached")):
+                               ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
+                               ("reg", "reg_errors"), ("l1", "l1_errors")):
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
