@@ -62,9 +62,9 @@ BINDING_SOURCES = ["bindings.cpp"]
 BENCH_SOURCES = ["loadgen.cpp", "bench_bindings.cpp"]  # in HARNESS_DIR
 FUZZ_TARGETS = ("pbwire", "hpack", "grpc", "http")
 FUZZ_DIR = os.path.join(HARNESS_DIR, "fuzz")
-CANARY_SOURCES = [os.path.join(PKG_DIR, "ops", f) for f in ("canary.hip", "datapath.hip", "sites.hip", "fabric.hip",
-                                                               "cumem.hip")]
-CANARY_HEADERS = [os.path.join(PKG_DIR, "ops", "canary_common.h")]
+CANARY_SOURCES = [os.path.join(PKG_DIR, "ops", f) for f in ("canary.hip", "hbm.hip", "gemm.hip", "datapath.hip",
+                                                               "sites.hip", "fabric.hip", "cumem.hip")]
+CANARY_HEADERS = [os.path.join(PKG_DIR, "ops", f) for f in ("canary_common.h", "canary_host.h")]
 CANARY_LIB = os.path.join(PKG_DIR, "ops", "libamdgpu_canary.so")
 
 

@@ -1,8 +1,9 @@
-"""Python face of the gfx950 health canary (``ops/canary.hip``).
+"""Python face of the gfx950 health canary (``ops/canary.hip`` and the sources named below;
+the C ABI mirrored here is declared in ``ops/canary_common.h``).
 
 ``run(device)`` loads ``libamdgpu_canary.so`` with ctypes (no torch needed) and runs
-the HBM pattern test, the MFMA exactness/throughput probe, the matrix-path check
-(an LDS-staged MFMA GEMM on exact integer data with ABFT row/column checksums), the
+the HBM pattern test (``hbm.hip``), the MFMA exactness/throughput probe, the matrix-path check
+(``gemm.hip``: an LDS-staged MFMA GEMM on exact integer data with ABFT row/column checksums), the
 fp8 / bf8 / fp4 MFMA exactness and rate checks, the LDS march (``datapath.hip``), the
 site probe (``sites.hip``: MFMA and vector-ALU exactness on every CU and SIMD, each
 mismatch located), the fabric check (``fabric.hip``: a march through each XCD's L2, a

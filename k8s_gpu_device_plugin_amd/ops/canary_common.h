@@ -1,8 +1,10 @@
-// Helpers shared by the gfx950 canary sources (canary.hip, datapath.hip, sites.hip,
-// fabric.hip, cumem.hip): the hash that derives exact small-integer operands, the MFMA
-// register vector types, the bf16 / OCP low-precision operand packing, the s_getreg
-// immediates, site_id(), and the C ABI of the site probe, the fabric check and the CU
-// memory check.
+// Shared by every gfx950 canary source (canary.hip, hbm.hip, gemm.hip, datapath.hip,
+// sites.hip, fabric.hip, cumem.hip).  Device side: the hash that derives exact small-integer
+// operands, the MFMA register vector types, the bf16 / OCP low-precision operand packing,
+// the s_getreg immediates, site_id(), the wave and block error reductions.  And the C ABI,
+// declared here once: every result struct that canary.py mirrors with ctypes, with its size
+// pinned, and the prototype of every exported entry point that another source calls.  The
+// host-side helpers are in canary_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +13,7 @@
 namespace canary {
 
 constexpr int kWave = 64;
+constexpr int kMaxBlocks = 4096;  // grid cap of the located checks: the index of a wave of 4-wave workgroups < 2^14
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
@@ -50,6 +53,7 @@ __device__ __forceinline__ short bf16_of_int(int v) {
 }
 
 using i32x8 = __attribute__((ext_vector_type(8))) int;
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 constexpr int kFp8 = 0, kBf8 = 1, kFp4 = 4;  // cbsz / blgp format codes
 constexpr int kFp8Unscaled = 8;             // host-side id of v_mfma_f32_32x32x16_fp8_fp8
@@ -90,6 +94,33 @@ __device__ __forceinline__ int scale_exp(int vary, int rc, int kb, int which) {
               : 0;
 }
 
+// Sum over the wave; lane 0 holds it.  One loop, two spellings: which one a kernel calls changes
+// the registers the compiler allocates and how it unrolls the kernel's other loops (mfma_exact:
+// 32 VGPRs in place, 46 by value).  In place: mfma_exact, lowp_exact, fp8_exact, lds_march; by
+// value: all others.  Compare the kernel-resource-usage remarks before changing a call site.
+__device__ __forceinline__ void wave_sum(uint32_t& v) {
+  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+}
+__device__ __forceinline__ uint32_t wave_total(uint32_t v) {
+  wave_sum(v);
+  return v;
+}
+
+// Block total of `bad`, then one atomic per block that saw any.  Every thread of a block of
+// at most 256 calls it.
+__device__ __forceinline__ void block_add_errors(uint32_t bad, unsigned long long* __restrict__ errors) {
+  bad = wave_total(bad);
+  __shared__ uint32_t wave_bad[256 / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
+  if (lane == 0) wave_bad[wid] = bad;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    uint32_t t = 0;
+    for (int w = 0; w < static_cast<int>(blockDim.x / kWave); ++w) t += wave_bad[w];
+    if (t) atomicAdd(errors, static_cast<unsigned long long>(t));
+  }
+}
+
 }  // namespace canary
 
 // ---- site probe (sites.hip): where on the chip each exactness check ran ----------------
@@ -110,6 +141,56 @@ __device__ __forceinline__ uint32_t site_id() {
 }  // namespace canary
 
 extern "C" {
+
+// ---- the whole run (canary.hip) and the entry points it calls in hbm.hip, gemm.hip, datapath.hip ----
+struct amdgpu_canary_result {
+  int ok;
+  int device;
+  unsigned long long hbm_bytes;
+  unsigned long long hbm_errors;
+  unsigned long long mfma_errors;
+  double write_gbps;
+  double read_gbps;
+  double mfma_tflops;
+  double elapsed_ms;
+  int num_cus;
+  char arch[64];
+  char error[256];
+  double gemm_tflops;                   // LDS-staged MFMA GEMM (matrix path) rate
+  unsigned long long gemm_errors;       // ABFT row/column checksum mismatches
+  double fp8_tflops;                    // block-scaled fp8 MFMA rate (datapath.hip)
+  double fp4_tflops;                    // block-scaled fp4 MFMA rate
+  unsigned long long lowp_errors;       // fp8 / bf8 / fp4 MFMA exactness mismatches
+  unsigned long long lds_errors;        // LDS march mismatches
+  unsigned long long lds_bytes;         // LDS bytes per workgroup the march covered
+  unsigned long long site_errors;       // site probe (sites.hip): wrong mfma + lowp + valu results + unlocated
+  int cus_reached;                      // CUs the site probe ran on
+  int simds_reached;                    // (CU, SIMD) sites it ran on
+  int cus_unreached;                    // num_cus - cus_reached: reported, does not fail the run
+  double site_ms;                       // device time of the site probe's launches
+  int n_bad_sites;                      // sites with a wrong result
+  unsigned int bad_sites[16];           // the first 16 of them, packed (below)
+  unsigned long long l2_errors;         // fabric check (fabric.hip): wrong words of the L2 march, unlocated included
+  unsigned long long xcd_errors;        // wrong words of the cross-XCD exchange
+  unsigned long long atomic_errors;     // wrong elements of the global-atomic tables
+  double l2_gbps;                       // bytes the march read back / its device time (a lower bound)
+  double fabric_ms;                     // device time of the fabric check's three launches
+  int xccs_reached;                     // XCDs the march ran on
+  int xcd_pairs_reached;                // (writer, reader) XCD pairs the exchange covered
+  int xcd_pairs_unreached;              // xccs_reached^2 - pairs reached: reported, does not fail the run
+};
+
+struct amdgpu_canary_datapath_result {  // datapath.hip; no ctypes mirror
+  double fp8_tflops;                // block-scaled fp8 (e4m3) MFMA, dense
+  double fp4_tflops;                // block-scaled fp4 (e2m1) MFMA, dense
+  unsigned long long lowp_errors;   // wrong accumulators over fp8 / bf8 / fp4 / unscaled fp8
+  unsigned long long lds_errors;    // LDS march mismatches
+  unsigned long long lds_bytes;     // LDS bytes per workgroup the march covered
+};
+
+int amdgpu_canary_datapaths(int device, int iters, amdgpu_canary_datapath_result* out, char* err, int err_len);
+int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flags, int kernel, double* tflops,
+                            unsigned long long* errors, char* err, int err_len);
 
 constexpr int kSiteChecks = 3;  // 0 mfma, 1 lowp, 2 valu
 
@@ -231,3 +312,14 @@ int amdgpu_canary_cu_describe(const amdgpu_canary_cu_result* r, const amdgpu_can
                               int len);
 
 }  // extern "C"
+
+// The sizes canary.py's ctypes mirrors have (tests/test_canary_abi.py pins the same numbers).
+static_assert(sizeof(amdgpu_canary_result) == 608, "canary.CanaryResult");
+static_assert(sizeof(amdgpu_canary_datapath_result) == 40, "no mirror: five 8-byte fields");
+static_assert(sizeof(amdgpu_canary_site_slot) == 16, "canary.SiteSlot");
+static_assert(sizeof(amdgpu_canary_sites_result) == 144, "canary.SitesResult");
+static_assert(sizeof(amdgpu_canary_xcc_slot) == 24, "canary.XccSlot");
+static_assert(sizeof(amdgpu_canary_pair_slot) == 16, "canary.PairSlot");
+static_assert(sizeof(amdgpu_canary_fabric_result) == 224, "canary.FabricResult");
+static_assert(sizeof(amdgpu_canary_cu_slot) == 16, "canary.CuSlot");
+static_assert(sizeof(amdgpu_canary_cu_result) == 176, "canary.CuResult");

@@ -37,23 +37,19 @@
 #include <cstring>
 #include <vector>
 
-#include "canary_common.h"
+#include "canary_host.h"
 
 namespace {
 
 using namespace canary;
 
 constexpr int kCuWaves = 4;      // waves per workgroup: one per SIMD of a CU
-constexpr int kMaxBlocks = 4096; // global wave index < 2^14
-constexpr int kMaxLdsBytes = 160 * 1024;
 // Values each lane keeps pinned: 480 of the 512 entries.  At -O3 this builds with no scratch
 // and 13 accumulator entries to spare; the other VGPRs hold base, the counters and
 // temporaries.  240 / 248 still builds without scratch but takes every entry, and pairs in
 // between (232 / 248) spill, so the margin is kept.
 constexpr int kNV = 240, kNA = 240;
 constexpr int kInjectLane = 3, kInjectBit = 9, kInjectVgpr = 5, kInjectAgpr = 7;
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 // K(i): (2i + 1) * odd is injective mod 2^32.  VGPR value i takes K(i), AGPR value i K(256 + i).
 constexpr uint32_t reg_key(int i) { return (2u * static_cast<uint32_t>(i) + 1u) * 0x9E3779B1u; }
@@ -64,11 +60,6 @@ __device__ __forceinline__ u32x4 cu_pattern(uint64_t idx) {
   const uint32_t b = lo * 0x9E3779B1u ^ (hi + 0xC0DEu) * 0x85EBCA77u;
   u32x4 v = {b, b ^ 0xA5A5A5A5u, ~b, b * 3u + 0x6A09E667u};
   return v;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;  // lane 0 holds the sum
 }
 
 #define PIN_V(x) asm volatile("" : "+v"(x))
@@ -143,8 +134,8 @@ __global__ void __launch_bounds__(256) reg_march(int reps, int inject_kind, int 
     }
     base = base * 0x85EBCA77u + 0x6A09E667u;  // 5
   }
-  bad_v = wave_sum(bad_v);
-  bad_a = wave_sum(bad_a);
+  bad_v = wave_total(bad_v);
+  bad_a = wave_total(bad_a);
   const uint32_t site_after = site_id();
   if (lane != 0) return;
   if (wave_site != nullptr && static_cast<int>(gw) < wave_site_len) wave_site[gw] = site;
@@ -205,8 +196,8 @@ __global__ void __launch_bounds__(256) l1_march(const u32x4* buf, int slice_word
     __syncthreads();  // every line of the slice has been brought in before anyone re-reads
     asm volatile("" ::: "memory");
   }
-  bad = wave_sum(bad);
-  bad_fill = wave_sum(bad_fill);
+  bad = wave_total(bad);
+  bad_fill = wave_total(bad_fill);
   const uint32_t site_after = site_id();
   if (lane != 0) return;
   if (wave_site != nullptr && static_cast<int>(gw) < wave_site_len) wave_site[gw] = site;
@@ -218,26 +209,6 @@ __global__ void __launch_bounds__(256) l1_march(const u32x4* buf, int slice_word
     atomicAdd(&counters[2], 1u);
     if (bad) atomicAdd(&counters[3], bad);
   }
-}
-
-// One l1_march launch with the largest dynamic LDS allocation the device grants (the
-// selection of launch_site_probe in sites.hip); false on a HIP error.
-bool launch_l1_march(const hipDeviceProp_t& prop, int blocks, const u32x4* buf, int slice_words, int l1_reps,
-                     int inject_wgs, amdgpu_canary_cu_slot* table, unsigned int* cu_waves, unsigned int* counters,
-                     unsigned int* wave_site, int wave_site_len) {
-  size_t bytes = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor : 0;
-  if (bytes > static_cast<size_t>(kMaxLdsBytes)) bytes = kMaxLdsBytes;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (attempt == 1 || bytes == 0) bytes = prop.sharedMemPerBlock;
-    bytes &= ~static_cast<size_t>(1023);
-    if (bytes == 0) return false;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(l1_march), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(bytes));
-    hipLaunchKernelGGL(l1_march, dim3(blocks), dim3(kCuWaves * kWave), bytes, 0, buf, slice_words, l1_reps,
-                       inject_wgs, table, cu_waves, counters, wave_site, wave_site_len);
-    if (hipGetLastError() == hipSuccess) return true;
-  }
-  return false;
 }
 
 // Fills the located totals and the coverage counts of `r` from host copies of the tables.
@@ -264,11 +235,6 @@ void summarize(const amdgpu_canary_cu_slot* t, const unsigned int* cu_waves, amd
     r->cus_reached += any;
     r->l1_cus_reached += cu_waves[cu] > 0;
   }
-}
-
-int format_cu(unsigned int site, char* buf, int len) {
-  return std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
-                       (site >> 2) & 0xFu);
 }
 
 }  // namespace
@@ -301,7 +267,7 @@ int amdgpu_canary_cu_describe(const amdgpu_canary_cu_result* r, const amdgpu_can
     if (first < 0)  // every wave that saw one moved while it marched
       return std::snprintf(buf, len, "register check: %llu wrong words at an unknown site", reg);
     char where[48];
-    amdgpu_canary_format_site(static_cast<unsigned int>(first), where, sizeof(where));
+    format_site(static_cast<unsigned int>(first), true, where, sizeof(where));
     int n = std::snprintf(buf, len, "register check: %llu wrong words at %s (%s", reg, where,
                           r->vgpr_errors && r->agpr_errors ? "vgpr+agpr" : r->agpr_errors ? "agpr" : "vgpr");
     if (sites > 1 && n > 0 && n < len)
@@ -319,7 +285,7 @@ int amdgpu_canary_cu_describe(const amdgpu_canary_cu_result* r, const amdgpu_can
     }
     if (first < 0) return std::snprintf(buf, len, "l1 check: %llu wrong words at an unknown cu", r->l1_errors);
     char where[48];
-    format_cu(static_cast<unsigned int>(first) << 2, where, sizeof(where));
+    format_site(static_cast<unsigned int>(first) << 2, false, where, sizeof(where));
     int n = std::snprintf(buf, len, "l1 check: %llu wrong words at %s", r->l1_errors, where);
     if (cus > 1 && n > 0 && n < len)
       n += std::snprintf(buf + n, len - n, " (+%d more cu%s)", cus - 1, cus > 2 ? "s" : "");
@@ -353,75 +319,68 @@ int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, i
   std::vector<amdgpu_canary_cu_slot> own_table(table_out ? 0 : kSiteSlots);
   amdgpu_canary_cu_slot* table = table_out ? table_out : own_table.data();
   std::vector<unsigned int> cu_waves(kSiteSlots / 4, 0);
+  Status st;
   hipDeviceProp_t prop;
   unsigned int h_counters[5] = {0, 0, 0, 0, 0};
-  amdgpu_canary_cu_slot* d_table = nullptr;
-  unsigned int *d_cu_waves = nullptr, *d_counters = nullptr, *d_wave_site = nullptr;
-  u32x4* d_buf = nullptr;
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  const size_t table_bytes = sizeof(amdgpu_canary_cu_slot) * kSiteSlots;
-  const size_t cu_bytes = sizeof(unsigned int) * (kSiteSlots / 4);
-  const size_t ws_bytes = sizeof(unsigned int) * 2 * static_cast<size_t>(wave_site_len);
+  DeviceBuffer<amdgpu_canary_cu_slot> d_table;
+  DeviceBuffer<unsigned int> d_cu_waves, d_counters, d_wave_site;
+  DeviceBuffer<u32x4> d_buf;
+  Events<3> ev;
   const int slice_words = l1_kb * 64;  // 16-B words; a multiple of 256
-  const char* what = "";
   int grid = 0;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e == hipSuccess) {
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  if (st.ok()) {
     grid = blocks == 0 ? 2 * prop.multiProcessorCount : blocks;
     if (grid > kMaxBlocks) grid = kMaxBlocks;
     if (grid < 1) grid = 1;
-    e = hipMalloc(&d_buf, static_cast<size_t>(grid) * slice_words * sizeof(u32x4));
   }
-  if (e == hipSuccess) e = hipMalloc(&d_table, table_bytes);
-  if (e == hipSuccess) e = hipMemset(d_table, 0, table_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_cu_waves, cu_bytes);
-  if (e == hipSuccess) e = hipMemset(d_cu_waves, 0, cu_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_counters, sizeof(h_counters));
-  if (e == hipSuccess) e = hipMemset(d_counters, 0, sizeof(h_counters));
-  if (e == hipSuccess && wave_site_len > 0) {
-    e = hipMalloc(&d_wave_site, ws_bytes);
-    if (e == hipSuccess) e = hipMemset(d_wave_site, 0xFF, ws_bytes);
+  CANARY_HIP(st, d_buf.alloc(static_cast<size_t>(grid) * slice_words * sizeof(u32x4)));
+  CANARY_HIP(st, d_table.alloc(sizeof(amdgpu_canary_cu_slot) * kSiteSlots));
+  CANARY_HIP(st, d_table.zero());
+  CANARY_HIP(st, d_cu_waves.alloc(sizeof(unsigned int) * cu_waves.size()));
+  CANARY_HIP(st, d_cu_waves.zero());
+  CANARY_HIP(st, d_counters.alloc(sizeof(h_counters)));
+  CANARY_HIP(st, d_counters.zero());
+  if (wave_site_len > 0) {
+    CANARY_HIP(st, d_wave_site.alloc(sizeof(unsigned int) * 2 * static_cast<size_t>(wave_site_len)));
+    CANARY_HIP(st, d_wave_site.fill(0xFF));
   }
-  for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  if (e == hipSuccess) {
+  CANARY_HIP(st, ev.create());
+  if (st.ok()) {
     out->cus_expected = prop.multiProcessorCount;
     const int max_launches = blocks == 0 ? 4 : 1;
-    for (int l = 0; e == hipSuccess && l < max_launches; ++l) {
-      float reg_ms = 0, l1_ms = 0;
+    for (int l = 0; l < max_launches; ++l) {
+      float ms[2] = {0, 0};  // reg_march; l1_fill and l1_march
       const int inj = l == 0 ? inject_kind : -1;
-      e = hipEventRecord(ev[0], 0);
-      if (e == hipSuccess) {
-        hipLaunchKernelGGL(reg_march, dim3(grid), dim3(kCuWaves * kWave), 0, 0, reps, inj,
-                           inj == 0 || inj == 1 ? inject_waves : 0, static_cast<uint32_t>(l), d_table, d_counters,
-                           l == 0 ? d_wave_site : nullptr, l == 0 ? wave_site_len : 0);
-        e = hipGetLastError();
-        what = "reg_march: ";
-      }
-      if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
-      if (e == hipSuccess && l == 0) {  // the pattern does not change: one fill serves every launch
-        hipLaunchKernelGGL(l1_fill, dim3(grid), dim3(kCuWaves * kWave), 0, 0, d_buf, slice_words);
-        e = hipGetLastError();
-        what = "l1_fill: ";
-      }
-      if (e == hipSuccess &&
-          !launch_l1_march(prop, grid, d_buf, slice_words, l1_reps, inj == 2 ? inject_waves : 0, d_table, d_cu_waves,
-                           d_counters, l == 0 && d_wave_site ? d_wave_site + wave_site_len : nullptr,
-                           l == 0 ? wave_site_len : 0)) {
-        what = "l1_march launch: ";
-        e = hipErrorLaunchFailure;
-      }
-      if (e == hipSuccess) e = hipEventRecord(ev[2], 0);
-      if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e == hipSuccess) e = hipEventElapsedTime(&reg_ms, ev[0], ev[1]);
-      if (e == hipSuccess) e = hipEventElapsedTime(&l1_ms, ev[1], ev[2]);
-      if (e == hipSuccess) what = "";
-      if (e == hipSuccess) e = hipMemcpy(table, d_table, table_bytes, hipMemcpyDeviceToHost);
-      if (e == hipSuccess) e = hipMemcpy(cu_waves.data(), d_cu_waves, cu_bytes, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) break;
-      out->reg_ms += reg_ms;
-      out->l1_ms += l1_ms;
+      time_stages(st, ev, ms, [&](int k) {
+        if (k == 0) {
+          st.stage("reg_march: ");
+          hipLaunchKernelGGL(reg_march, dim3(grid), dim3(kCuWaves * kWave), 0, 0, reps, inj,
+                             inj == 0 || inj == 1 ? inject_waves : 0, static_cast<uint32_t>(l), d_table.get(),
+                             d_counters.get(), l == 0 ? d_wave_site.get() : nullptr, l == 0 ? wave_site_len : 0);
+          return hipGetLastError();
+        }
+        if (l == 0) {  // the pattern does not change: one fill serves every launch
+          st.stage("l1_fill: ");
+          hipLaunchKernelGGL(l1_fill, dim3(grid), dim3(kCuWaves * kWave), 0, 0, d_buf.get(), slice_words);
+          const hipError_t e = hipGetLastError();
+          if (e != hipSuccess) return e;
+        }
+        if (launch_with_max_lds(l1_march, prop, dim3(grid), dim3(kCuWaves * kWave), d_buf.get(), slice_words, l1_reps,
+                                inj == 2 ? inject_waves : 0, d_table.get(), d_cu_waves.get(), d_counters.get(),
+                                l == 0 && d_wave_site.get() ? d_wave_site.get() + wave_site_len : nullptr,
+                                l == 0 ? wave_site_len : 0))
+          return hipSuccess;
+        st.stage("l1_march launch: ");
+        return hipErrorLaunchFailure;
+      });
+      st.stage("");
+      CANARY_HIP(st, d_table.download(table));
+      CANARY_HIP(st, d_cu_waves.download(cu_waves.data()));
+      if (!st.ok()) break;
+      out->reg_ms += ms[0];
+      out->l1_ms += ms[1];
       out->launches = l + 1;
       summarize(table, cu_waves.data(), out);
       if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected &&
@@ -429,22 +388,14 @@ int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, i
         break;
     }
   }
-  if (e == hipSuccess) e = hipMemcpy(h_counters, d_counters, sizeof(h_counters), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && wave_site_len > 0) e = hipMemcpy(wave_site_out, d_wave_site, ws_bytes, hipMemcpyDeviceToHost);
+  CANARY_HIP(st, d_counters.download(h_counters));
+  if (wave_site_len > 0) CANARY_HIP(st, d_wave_site.download(wave_site_out));
   out->moved = h_counters[0];
   out->unlocated_errors = h_counters[1];
   out->l1_moved = h_counters[2];
   out->l1_errors += h_counters[3];
   out->l1_fill_errors = h_counters[4];
-  if (e != hipSuccess) std::snprintf(err, err_len, "cu check: %s%s", what, hipGetErrorString(e));
-  for (int i = 0; i < 3; ++i)
-    if (ev[i]) (void)hipEventDestroy(ev[i]);
-  if (d_wave_site) (void)hipFree(d_wave_site);
-  if (d_counters) (void)hipFree(d_counters);
-  if (d_cu_waves) (void)hipFree(d_cu_waves);
-  if (d_table) (void)hipFree(d_table);
-  if (d_buf) (void)hipFree(d_buf);
-  return e == hipSuccess ? 0 : -1;
+  return st.report("cu check: ", err, err_len);
 }
 
 }  // extern "C"

@@ -38,7 +38,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "canary_common.h"
+#include "canary_host.h"
 
 namespace {
 
@@ -78,7 +78,7 @@ __global__ void __launch_bounds__(64) lowp_exact(int ksteps, int vary_scale, int
     }
     bad += acc[reg] != static_cast<float>(ref);
   }
-  for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off, kWave);
+  wave_sum(bad);
   if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
 }
 
@@ -110,7 +110,7 @@ __global__ void __launch_bounds__(64) fp8_exact(int ksteps, int inject_blocks, u
     for (int k = 0; k < ksteps * 16; ++k) ref += a_val(blk, row, k) * b_val(blk, k, col);
     bad += acc[reg] != static_cast<float>(ref);
   }
-  for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off, kWave);
+  wave_sum(bad);
   if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
 }
 
@@ -212,157 +212,115 @@ __global__ void __launch_bounds__(256) lds_march(int words, uint32_t seed, int i
   }
   __syncthreads();
   for (int i = t; i < words; i += nt) bad += lds[i] != ~lds_pat(i, s);
-  for (int off = kWave / 2; off > 0; off >>= 1) bad += __shfl_down(bad, off, kWave);
+  wave_sum(bad);
   // no __shared__ scratch: the dynamic allocation is the whole LDS
   if ((t & (kWave - 1)) == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
 }
 
-constexpr int kMaxLdsBytes = 160 * 1024;
-
 // Launches lds_march over 2 workgroups per CU with the largest LDS allocation the device
 // grants (160 KB on gfx950); returns its size in bytes, 0 on a HIP error.
 unsigned long long launch_lds_march(const hipDeviceProp_t& prop, int inject_blocks, unsigned long long* d_err) {
-  size_t bytes = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor : 0;
-  if (bytes > static_cast<size_t>(kMaxLdsBytes)) bytes = kMaxLdsBytes;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (attempt == 1 || bytes == 0) bytes = prop.sharedMemPerBlock;
-    bytes &= ~static_cast<size_t>(1023);
-    if (bytes == 0) return 0;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(lds_march), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(bytes));
-    hipLaunchKernelGGL(lds_march, dim3(prop.multiProcessorCount * 2), dim3(256), bytes, 0,
-                       static_cast<int>(bytes / 4), 0xC0FFEEu, inject_blocks, d_err);
-    if (hipGetLastError() == hipSuccess) return bytes;
-  }
-  return 0;
+  return launch_with_max_lds(lds_march, prop, dim3(prop.multiProcessorCount * 2), dim3(256), granted_lds_words{},
+                             0xC0FFEEu, inject_blocks, d_err);
 }
 
-template <int FMT>
-float time_lowp_rate(int blocks, int iters, float* sink) {
-  hipEvent_t e0, e1;
-  float ms = 0;
-  if (hipEventCreate(&e0) != hipSuccess) return 0;
-  if (hipEventCreate(&e1) != hipSuccess) {
-    (void)hipEventDestroy(e0);
-    return 0;
-  }
-  hipLaunchKernelGGL(lowp_rate<FMT>, dim3(blocks), dim3(256), 0, 0, 16, sink);  // warm-up
-  (void)hipEventRecord(e0, 0);
-  hipLaunchKernelGGL(lowp_rate<FMT>, dim3(blocks), dim3(256), 0, 0, iters, sink);
-  (void)hipEventRecord(e1, 0);
-  if (hipEventSynchronize(e1) != hipSuccess || hipGetLastError() != hipSuccess ||
-      hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-    ms = 0;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
-  return ms;
+// The instantiation of a block-scaled kernel for format code `fmt`; null for any other code.
+template <typename K>
+K by_format(int fmt, K fp8, K bf8, K fp4) {
+  return fmt == kFp8 ? fp8 : fmt == kBf8 ? bf8 : fmt == kFp4 ? fp4 : nullptr;
+}
+
+// Device ms of one lowp_rate launch of `iters` MFMA pairs per wave, after a warm-up one; 0 on a
+// HIP error or an unknown format.
+float time_lowp_rate(Status& st, int fmt, int blocks, int iters, float* sink) {
+  const auto kernel = by_format(fmt, lowp_rate<kFp8>, lowp_rate<kBf8>, lowp_rate<kFp4>);
+  Events<2> ev;
+  float ms[1] = {0};
+  CANARY_HIP(st, ev.create());
+  if (!st.ok() || kernel == nullptr) return 0;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0, 16, sink);  // warm-up
+  time_stages(st, ev, ms, [&](int) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0, iters, sink);
+    return hipSuccess;
+  });
+  return st.ok() ? ms[0] : 0;
 }
 
 bool launch_lowp_exact(int fmt, int blocks, int ksteps, int vary, int inject, unsigned long long* d_err) {
-  switch (fmt) {
-    case kFp8: hipLaunchKernelGGL(lowp_exact<kFp8>, dim3(blocks), dim3(64), 0, 0, ksteps, vary, inject, d_err); break;
-    case kBf8: hipLaunchKernelGGL(lowp_exact<kBf8>, dim3(blocks), dim3(64), 0, 0, ksteps, vary, inject, d_err); break;
-    case kFp4: hipLaunchKernelGGL(lowp_exact<kFp4>, dim3(blocks), dim3(64), 0, 0, ksteps, vary, inject, d_err); break;
-    case kFp8Unscaled:
-      hipLaunchKernelGGL(fp8_exact, dim3(blocks), dim3(64), 0, 0, 4 * ksteps, inject, d_err);
-      break;
-    default: return false;
-  }
+  if (fmt == kFp8Unscaled)
+    hipLaunchKernelGGL(fp8_exact, dim3(blocks), dim3(64), 0, 0, 4 * ksteps, inject, d_err);
+  else if (const auto kernel = by_format(fmt, lowp_exact<kFp8>, lowp_exact<kBf8>, lowp_exact<kFp4>))
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64), 0, 0, ksteps, vary, inject, d_err);
+  else
+    return false;
   return hipGetLastError() == hipSuccess;
 }
 
 }  // namespace
 
-extern "C" {
 
-struct amdgpu_canary_datapath_result {
-  double fp8_tflops;                // block-scaled fp8 (e4m3) MFMA, dense
-  double fp4_tflops;                // block-scaled fp4 (e2m1) MFMA, dense
-  unsigned long long lowp_errors;   // wrong accumulators over fp8 / bf8 / fp4 / unscaled fp8
-  unsigned long long lds_errors;    // LDS march mismatches
-  unsigned long long lds_bytes;     // LDS bytes per workgroup the march covered
-};
+extern "C" {
 
 // Exactness of every low-precision MFMA form (2 blocks per CU each, K = 256, varied block
 // scales), the LDS march, and the fp8 / fp4 rates (`iters` MFMA pairs per wave).
 int amdgpu_canary_datapaths(int device, int iters, amdgpu_canary_datapath_result* out, char* err, int err_len) {
   std::memset(out, 0, sizeof(*out));
+  Status st;
   hipDeviceProp_t prop;
-  unsigned long long* d_err = nullptr;
-  float* sink = nullptr;
+  DeviceBuffer<unsigned long long> d_err;  // [0] lowp, [1] lds
+  DeviceBuffer<float> sink;
   unsigned long long h_err[2] = {0, 0};
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e == hipSuccess) e = hipMalloc(&d_err, sizeof(h_err));
-  if (e == hipSuccess) e = hipMemset(d_err, 0, sizeof(h_err));
-  if (e == hipSuccess) e = hipMalloc(&sink, static_cast<size_t>(prop.multiProcessorCount) * 8 * 256 * sizeof(float));
-  if (e == hipSuccess) {
-    const int blocks = prop.multiProcessorCount * 2;
-    for (int fmt : {kFp8, kBf8, kFp4, kFp8Unscaled})
-      if (!launch_lowp_exact(fmt, blocks, 4, 1, 0, d_err)) {
-        e = hipErrorLaunchFailure;
-        break;
-      }
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  CANARY_HIP(st, d_err.alloc(sizeof(h_err)));
+  CANARY_HIP(st, d_err.zero());
+  CANARY_HIP(st, sink.alloc(static_cast<size_t>(prop.multiProcessorCount) * 8 * 256 * sizeof(float)));
+  for (int fmt : {kFp8, kBf8, kFp4, kFp8Unscaled})
+    if (st.ok() && !launch_lowp_exact(fmt, prop.multiProcessorCount * 2, 4, 1, 0, d_err.get())) st.fail("");
+  if (st.ok()) {
+    out->lds_bytes = launch_lds_march(prop, 0, d_err.get() + 1);
+    if (out->lds_bytes == 0) st.fail("");
   }
-  if (e == hipSuccess) {
-    out->lds_bytes = launch_lds_march(prop, 0, d_err + 1);
-    if (out->lds_bytes == 0) e = hipErrorLaunchFailure;
-  }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(h_err, d_err, sizeof(h_err), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) {
+  CANARY_HIP(st, hipDeviceSynchronize());
+  CANARY_HIP(st, d_err.download(h_err));
+  if (st.ok()) {
     out->lowp_errors = h_err[0];
     out->lds_errors = h_err[1];
     const int blocks = prop.multiProcessorCount * 8;
     if (iters < 1) iters = 1;
     const double flops = 2.0 * 32 * 32 * 64 * 2.0 /*chains*/ * iters * (blocks * 4.0 /*waves*/);
-    const float t8 = time_lowp_rate<kFp8>(blocks, iters, sink);
-    const float t4 = time_lowp_rate<kFp4>(blocks, iters, sink);
+    const float t8 = time_lowp_rate(st, kFp8, blocks, iters, sink.get());
+    const float t4 = time_lowp_rate(st, kFp4, blocks, iters, sink.get());
     out->fp8_tflops = t8 > 0 ? flops / (t8 * 1e-3) / 1e12 : 0;
     out->fp4_tflops = t4 > 0 ? flops / (t4 * 1e-3) / 1e12 : 0;
-    e = hipGetLastError();
   }
-  if (e != hipSuccess) std::snprintf(err, err_len, "datapaths: %s", hipGetErrorString(e));
-  if (sink) (void)hipFree(sink);
-  if (d_err) (void)hipFree(d_err);
-  return e == hipSuccess ? 0 : -1;
+  return st.report("datapaths: ", err, err_len);
 }
 
 // Wrong accumulator registers of one low-precision form (fmt 0 fp8, 1 bf8, 4 fp4: block
 // scaled, K = 64 * ksteps; 8: unscaled fp8, K = 64 * ksteps too) over 2 blocks per CU, of
 // which `inject_blocks` compute with one perturbed operand.  -1 on a HIP error.
 long long amdgpu_canary_lowp_check(int device, int fmt, int ksteps, int vary_scale, int inject_blocks) {
-  hipDeviceProp_t prop;
-  unsigned long long* d_err = nullptr;
-  unsigned long long h = 0;
-  if (ksteps < 1 || ksteps > 64 || inject_blocks < 0 || hipSetDevice(device) != hipSuccess ||
-      hipGetDeviceProperties(&prop, device) != hipSuccess)
-    return -1;
-  long long rc = -1;
-  if (hipMalloc(&d_err, 8) == hipSuccess && hipMemset(d_err, 0, 8) == hipSuccess &&
-      launch_lowp_exact(fmt, prop.multiProcessorCount * 2, ksteps, vary_scale, inject_blocks, d_err) &&
-      hipDeviceSynchronize() == hipSuccess && hipMemcpy(&h, d_err, 8, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = static_cast<long long>(h);
-  if (d_err) (void)hipFree(d_err);
-  return rc;
+  if (ksteps < 1 || ksteps > 64 || inject_blocks < 0) return -1;
+  return count_errors(device, [&](Status& st, const hipDeviceProp_t& prop, unsigned long long* d_err) {
+    if (!launch_lowp_exact(fmt, prop.multiProcessorCount * 2, ksteps, vary_scale, inject_blocks, d_err)) st.fail("");
+  });
 }
 
 // Dense TFLOP/s of the block-scaled form `fmt` (0 fp8, 1 bf8, 4 fp4); -1 on error.
 int amdgpu_canary_lowp_rate(int device, int fmt, int iters, double* tflops) {
-  hipDeviceProp_t prop;
-  float* sink = nullptr;
   *tflops = 0;
-  if (iters < 1 || hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess) return -1;
+  if (iters < 1) return -1;
+  Status st;
+  hipDeviceProp_t prop;
+  DeviceBuffer<float> sink;
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  if (!st.ok()) return -1;
   const int blocks = prop.multiProcessorCount * 8;
-  if (hipMalloc(&sink, static_cast<size_t>(blocks) * 256 * sizeof(float)) != hipSuccess) return -1;
-  float ms = 0;
-  switch (fmt) {
-    case kFp8: ms = time_lowp_rate<kFp8>(blocks, iters, sink); break;
-    case kBf8: ms = time_lowp_rate<kBf8>(blocks, iters, sink); break;
-    case kFp4: ms = time_lowp_rate<kFp4>(blocks, iters, sink); break;
-    default: break;
-  }
-  (void)hipFree(sink);
+  CANARY_HIP(st, sink.alloc(static_cast<size_t>(blocks) * 256 * sizeof(float)));
+  if (!st.ok()) return -1;
+  const float ms = time_lowp_rate(st, fmt, blocks, iters, sink.get());
   if (ms <= 0) return -1;
   *tflops = 2.0 * 32 * 32 * 64 * 2.0 * iters * (blocks * 4.0) / (ms * 1e-3) / 1e12;
   return 0;
@@ -371,20 +329,12 @@ int amdgpu_canary_lowp_rate(int device, int fmt, int iters, double* tflops) {
 // LDS march mismatches over 2 workgroups per CU (`inject_blocks` of them flip one bit);
 // *bytes = LDS bytes per workgroup covered.  -1 on a HIP error.
 long long amdgpu_canary_lds_check(int device, int inject_blocks, unsigned long long* bytes) {
-  hipDeviceProp_t prop;
-  unsigned long long* d_err = nullptr;
-  unsigned long long h = 0;
   *bytes = 0;
-  if (inject_blocks < 0 || hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&prop, device) != hipSuccess)
-    return -1;
-  long long rc = -1;
-  if (hipMalloc(&d_err, 8) == hipSuccess && hipMemset(d_err, 0, 8) == hipSuccess) {
+  if (inject_blocks < 0) return -1;
+  return count_errors(device, [&](Status& st, const hipDeviceProp_t& prop, unsigned long long* d_err) {
     *bytes = launch_lds_march(prop, inject_blocks, d_err);
-    if (*bytes && hipDeviceSynchronize() == hipSuccess && hipMemcpy(&h, d_err, 8, hipMemcpyDeviceToHost) == hipSuccess)
-      rc = static_cast<long long>(h);
-  }
-  if (d_err) (void)hipFree(d_err);
-  return rc;
+    if (*bytes == 0) st.fail("");
+  });
 }
 
 // Host wrapper for the numerics test (see lowp_gemm): all buffers in host memory.
@@ -394,60 +344,53 @@ int amdgpu_canary_lowp_gemm(int device, int fmt, const uint8_t* a_host, const ui
     std::snprintf(err, err_len, "fmt %d shape (%d,%d,%d): need fmt 0/1/4, M,N %% 32 == 0, K %% 64 == 0", fmt, M, N, K);
     return -1;
   }
-  uint8_t *a = nullptr, *bt = nullptr, *sa = nullptr, *sb = nullptr;
-  float* c = nullptr;
-  const size_t na = static_cast<size_t>(M) * K, nb = static_cast<size_t>(N) * K, nsa = static_cast<size_t>(M) * (K / 32),
-               nsb = static_cast<size_t>(N) * (K / 32), nc = static_cast<size_t>(M) * N * 4;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&a, na);
-  if (e == hipSuccess) e = hipMalloc(&bt, nb);
-  if (e == hipSuccess) e = hipMalloc(&sa, nsa);
-  if (e == hipSuccess) e = hipMalloc(&sb, nsb);
-  if (e == hipSuccess) e = hipMalloc(&c, nc);
-  if (e == hipSuccess) e = hipMemcpy(a, a_host, na, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(bt, bt_host, nb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(sa, sa_host, nsa, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(sb, sb_host, nsb, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    const dim3 grid(N / 32, M / 32);
-    if (fmt == kFp8) hipLaunchKernelGGL(lowp_gemm<kFp8>, grid, dim3(64), 0, 0, a, bt, sa, sb, c, M, N, K);
-    else if (fmt == kBf8) hipLaunchKernelGGL(lowp_gemm<kBf8>, grid, dim3(64), 0, 0, a, bt, sa, sb, c, M, N, K);
-    else hipLaunchKernelGGL(lowp_gemm<kFp4>, grid, dim3(64), 0, 0, a, bt, sa, sb, c, M, N, K);
-    e = hipGetLastError();
+  Status st;
+  DeviceBuffer<uint8_t> a, bt, sa, sb;
+  DeviceBuffer<float> c;
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, a.alloc(static_cast<size_t>(M) * K));
+  CANARY_HIP(st, bt.alloc(static_cast<size_t>(N) * K));
+  CANARY_HIP(st, sa.alloc(static_cast<size_t>(M) * (K / 32)));
+  CANARY_HIP(st, sb.alloc(static_cast<size_t>(N) * (K / 32)));
+  CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
+  CANARY_HIP(st, a.upload(a_host));
+  CANARY_HIP(st, bt.upload(bt_host));
+  CANARY_HIP(st, sa.upload(sa_host));
+  CANARY_HIP(st, sb.upload(sb_host));
+  if (st.ok()) {
+    const auto kernel = by_format(fmt, lowp_gemm<kFp8>, lowp_gemm<kBf8>, lowp_gemm<kFp4>);
+    hipLaunchKernelGGL(kernel, dim3(N / 32, M / 32), dim3(64), 0, 0, a.get(), bt.get(), sa.get(), sb.get(), c.get(), M, N,
+                       K);
+    st.check(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(c_host, c, nc, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) std::snprintf(err, err_len, "%s", hipGetErrorString(e));
-  for (void* p : {static_cast<void*>(a), static_cast<void*>(bt), static_cast<void*>(sa), static_cast<void*>(sb),
-                  static_cast<void*>(c)})
-    if (p) (void)hipFree(p);
-  return e == hipSuccess ? 0 : -1;
+  CANARY_HIP(st, hipDeviceSynchronize());
+  CANARY_HIP(st, c.download(c_host));
+  return st.report("", err, err_len);
 }
 
 // Raw-fragment probe (see lowp_raw): a, b [64][32] codes, sa, sb [64], c [32][32].
 int amdgpu_canary_lowp_raw(int device, int fmt, const uint8_t* a_host, const uint8_t* b_host, const uint8_t* sa_host,
                            const uint8_t* sb_host, float* c_host) {
   if (fmt != kFp8 && fmt != kBf8 && fmt != kFp4) return -1;
-  uint8_t* buf = nullptr;
-  float* c = nullptr;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipMalloc(&buf, 2 * 2048 + 2 * 64);
-  if (e == hipSuccess) e = hipMalloc(&c, 32 * 32 * 4);
-  if (e == hipSuccess) e = hipMemcpy(buf, a_host, 2048, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(buf + 2048, b_host, 2048, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(buf + 4096, sa_host, 64, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(buf + 4160, sb_host, 64, hipMemcpyHostToDevice);
-  if (e == hipSuccess) {
-    if (fmt == kFp8) hipLaunchKernelGGL(lowp_raw<kFp8>, dim3(1), dim3(64), 0, 0, buf, buf + 2048, buf + 4096, buf + 4160, c);
-    else if (fmt == kBf8) hipLaunchKernelGGL(lowp_raw<kBf8>, dim3(1), dim3(64), 0, 0, buf, buf + 2048, buf + 4096, buf + 4160, c);
-    else hipLaunchKernelGGL(lowp_raw<kFp4>, dim3(1), dim3(64), 0, 0, buf, buf + 2048, buf + 4096, buf + 4160, c);
-    e = hipGetLastError();
+  Status st;
+  DeviceBuffer<uint8_t> buf;  // a, b, sa, sb back to back
+  DeviceBuffer<float> c;
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, buf.alloc(2 * 2048 + 2 * 64));
+  CANARY_HIP(st, c.alloc(32 * 32 * 4));
+  uint8_t *a = buf.get(), *b = a + 2048, *sa = a + 4096, *sb = a + 4160;
+  CANARY_HIP(st, hipMemcpy(a, a_host, 2048, hipMemcpyHostToDevice));
+  CANARY_HIP(st, hipMemcpy(b, b_host, 2048, hipMemcpyHostToDevice));
+  CANARY_HIP(st, hipMemcpy(sa, sa_host, 64, hipMemcpyHostToDevice));
+  CANARY_HIP(st, hipMemcpy(sb, sb_host, 64, hipMemcpyHostToDevice));
+  if (st.ok()) {
+    const auto kernel = by_format(fmt, lowp_raw<kFp8>, lowp_raw<kBf8>, lowp_raw<kFp4>);
+    hipLaunchKernelGGL(kernel, dim3(1), dim3(64), 0, 0, a, b, sa, sb, c.get());
+    st.check(hipGetLastError());
   }
-  if (e == hipSuccess) e = hipDeviceSynchronize();
-  if (e == hipSuccess) e = hipMemcpy(c_host, c, 32 * 32 * 4, hipMemcpyDeviceToHost);
-  if (c) (void)hipFree(c);
-  if (buf) (void)hipFree(buf);
-  return e == hipSuccess ? 0 : -1;
+  CANARY_HIP(st, hipDeviceSynchronize());
+  CANARY_HIP(st, c.download(c_host));
+  return st.ok() ? 0 : -1;
 }
 
 }  // extern "C"

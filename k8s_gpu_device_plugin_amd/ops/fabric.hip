@@ -34,19 +34,16 @@
 #include <cstring>
 #include <vector>
 
-#include "canary_common.h"
+#include "canary_host.h"
 
 namespace {
 
 using namespace canary;
 
 constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 4096;
 constexpr int kInjectKinds = 3;  // 0 l2, 1 xcd, 2 atomic
 // the injected flip: bit 9 of 32-bit word 1 of 16-B word 37 (byte offset 0x254) of a slice
 constexpr int kInjectWord = 37, kInjectBit = 9;
-
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
 
 // The 16-B pattern of canary.hip's HBM test under a seed of its own: lo * odd constant is a
 // bijection mod 2^32, so no two 16-B words of the buffer (<= 4 GiB) share a pattern; with
@@ -529,12 +526,12 @@ int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inj
                   blocks, kMaxBlocks, slice_kb, reps, inject_kind, inject_op, inject_blocks);
     return -1;
   }
+  Status st;
   hipDeviceProp_t prop;
-  u32x4* d_buf = nullptr;
-  unsigned char *d_state = nullptr, *d_tables = nullptr;
-  int* d_lists = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  const char* what = "";
+  DeviceBuffer<u32x4> d_buf;
+  DeviceBuffer<unsigned char> d_state, d_tables;
+  DeviceBuffer<int> d_lists;
+  Events<3> ev;
   // device state of the march and the exchange, one allocation
   constexpr size_t kTableOff = 0, kMatrixOff = kTableOff + sizeof(amdgpu_canary_xcc_slot) * kFabricXccs,
                    kCountersOff = kMatrixOff + sizeof(amdgpu_canary_pair_slot) * kFabricXccs * kFabricXccs,
@@ -543,63 +540,54 @@ int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inj
   std::vector<unsigned char> h_state, h_tables(kTablesBytes + 256, 0), h_got, want;
   std::vector<int> h_lists;
   int grid = 0, slice_words = slice_kb * 64;
-  size_t state_bytes = 0;
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e == hipSuccess) {
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  if (st.ok()) {
     grid = blocks > 0 ? blocks : prop.multiProcessorCount;
     if (grid > kMaxBlocks) grid = kMaxBlocks;
     if (grid < 1) grid = 1;
     out->blocks = grid;
     out->slice_kb = slice_kb;
-    state_bytes = kSliceXccOff + sizeof(unsigned int) * grid;
-    h_state.assign(state_bytes, 0);
+    h_state.assign(kSliceXccOff + sizeof(unsigned int) * grid, 0);
     std::memset(h_state.data() + kFirstOff, 0xFF, sizeof(unsigned long long));  // no wrong word yet
     std::memset(h_state.data() + kSliceXccOff, 0xFF, sizeof(unsigned int) * grid);
     for (int op = 0; op < kAtomicOps; ++op) atomic_initial(op, h_tables.data() + table_offset(op));
-    e = hipMalloc(&d_buf, static_cast<size_t>(grid) * slice_words * sizeof(u32x4));
   }
-  if (e == hipSuccess) e = hipMalloc(&d_state, state_bytes);
-  if (e == hipSuccess) e = hipMemcpy(d_state, h_state.data(), state_bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d_tables, h_tables.size());
-  if (e == hipSuccess) e = hipMemcpy(d_tables, h_tables.data(), h_tables.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d_lists, sizeof(int) * (grid + kFabricXccs + 1));
-  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = hipEventCreate(&ev[i]);
-  if (e == hipSuccess) {
-    auto* d_table = reinterpret_cast<amdgpu_canary_xcc_slot*>(d_state + kTableOff);
-    auto* d_matrix = reinterpret_cast<amdgpu_canary_pair_slot*>(d_state + kMatrixOff);
-    auto* d_counters = reinterpret_cast<unsigned long long*>(d_state + kCountersOff);
-    auto* d_first = reinterpret_cast<unsigned long long*>(d_state + kFirstOff);
-    auto* d_slice_xcc = reinterpret_cast<unsigned int*>(d_state + kSliceXccOff);
-    float ms = 0;
+  CANARY_HIP(st, d_buf.alloc(static_cast<size_t>(grid) * slice_words * sizeof(u32x4)));
+  CANARY_HIP(st, d_state.alloc(h_state.size()));
+  CANARY_HIP(st, d_state.upload(h_state.data()));
+  CANARY_HIP(st, d_tables.alloc(h_tables.size()));
+  CANARY_HIP(st, d_tables.upload(h_tables.data()));
+  CANARY_HIP(st, d_lists.alloc(sizeof(int) * (grid + kFabricXccs + 1)));
+  CANARY_HIP(st, ev.create());
+  if (st.ok()) {
+    auto* d_table = reinterpret_cast<amdgpu_canary_xcc_slot*>(d_state.get() + kTableOff);
+    auto* d_matrix = reinterpret_cast<amdgpu_canary_pair_slot*>(d_state.get() + kMatrixOff);
+    auto* d_counters = reinterpret_cast<unsigned long long*>(d_state.get() + kCountersOff);
+    auto* d_first = reinterpret_cast<unsigned long long*>(d_state.get() + kFirstOff);
+    auto* d_slice_xcc = reinterpret_cast<unsigned int*>(d_state.get() + kSliceXccOff);
     // the atomics and the march, back to back
-    e = hipEventRecord(ev[0], 0);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(atomic_exact, dim3(grid), dim3(kThreads), 0, 0, d_tables, inject_op,
-                         inject_kind == 2 ? inject_blocks : 0);
-      e = hipGetLastError();
-      what = "atomic_exact: ";
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[1], 0);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(l2_march, dim3(grid), dim3(kThreads), 0, 0, d_buf, slice_words, reps, inject_kind,
-                         inject_kind == 0 || inject_kind == 1 ? inject_blocks : 0, d_table, d_slice_xcc, d_first,
-                         d_counters);
-      e = hipGetLastError();
-      what = "l2_march: ";
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[2], 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[0], ev[1]);
-    if (e == hipSuccess) out->atomic_ms = ms;
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[1], ev[2]);
-    if (e == hipSuccess) out->march_ms = ms;
-    if (e == hipSuccess) what = "";
+    float ms[2] = {0, 0};
+    time_stages(st, ev, ms, [&](int k) {
+      if (k == 0) {
+        st.stage("atomic_exact: ");
+        hipLaunchKernelGGL(atomic_exact, dim3(grid), dim3(kThreads), 0, 0, d_tables.get(), inject_op,
+                           inject_kind == 2 ? inject_blocks : 0);
+      } else {
+        st.stage("l2_march: ");
+        hipLaunchKernelGGL(l2_march, dim3(grid), dim3(kThreads), 0, 0, d_buf.get(), slice_words, reps, inject_kind,
+                           inject_kind == 0 || inject_kind == 1 ? inject_blocks : 0, d_table, d_slice_xcc, d_first,
+                           d_counters);
+      }
+      return hipGetLastError();
+    });
+    st.stage("");
+    out->atomic_ms = ms[0];
+    out->march_ms = ms[1];
     // the slices of each writer xcc, in slice order
-    if (e == hipSuccess)
-      e = hipMemcpy(h_state.data() + kSliceXccOff, d_slice_xcc, sizeof(unsigned int) * grid, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) {
+    CANARY_HIP(st, hipMemcpy(h_state.data() + kSliceXccOff, d_slice_xcc, sizeof(unsigned int) * grid,
+                             hipMemcpyDeviceToHost));
+    if (st.ok()) {
       const unsigned int* sx = reinterpret_cast<const unsigned int*>(h_state.data() + kSliceXccOff);
       h_lists.assign(kFabricXccs + 1, 0);  // list_off[17], then the lists
       for (int w = 0; w < kFabricXccs; ++w) {
@@ -608,28 +596,22 @@ int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inj
           if (sx[s] == static_cast<unsigned int>(w)) h_lists.push_back(s);
       }
       h_lists[kFabricXccs] = static_cast<int>(h_lists.size()) - (kFabricXccs + 1);  // <= grid
-      e = hipMemcpy(d_lists, h_lists.data(), sizeof(int) * h_lists.size(), hipMemcpyHostToDevice);
+      st.check(hipMemcpy(d_lists.get(), h_lists.data(), sizeof(int) * h_lists.size(), hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) e = hipEventRecord(ev[2], 0);
-    if (e == hipSuccess) {
-      hipLaunchKernelGGL(xcd_exchange, dim3(grid), dim3(kThreads), 0, 0, d_buf, slice_words, grid,
-                         d_lists + kFabricXccs + 1, d_lists, d_matrix, d_counters);
-      e = hipGetLastError();
-      what = "xcd_exchange: ";
-    }
-    if (e == hipSuccess) e = hipEventRecord(ev[3], 0);
-    if (e == hipSuccess) e = hipEventSynchronize(ev[3]);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ev[2], ev[3]);
-    if (e == hipSuccess) out->exchange_ms = ms;
-    if (e == hipSuccess) what = "";
+    float exchange_ms[1] = {0};
+    time_stages(st, ev, exchange_ms, [&](int) {
+      st.stage("xcd_exchange: ");
+      hipLaunchKernelGGL(xcd_exchange, dim3(grid), dim3(kThreads), 0, 0, d_buf.get(), slice_words, grid,
+                         d_lists.get() + kFabricXccs + 1, d_lists.get(), d_matrix, d_counters);
+      return hipGetLastError();
+    });
+    st.stage("");
+    out->exchange_ms = exchange_ms[0];
   }
-  if (e == hipSuccess) e = hipMemcpy(h_state.data(), d_state, state_bytes, hipMemcpyDeviceToHost);
-  if (e == hipSuccess) {
-    h_got.resize(h_tables.size());
-    e = hipMemcpy(h_got.data(), d_tables, h_got.size(), hipMemcpyDeviceToHost);
-  }
-  if (e == hipSuccess) {
+  CANARY_HIP(st, d_state.download(h_state.data()));
+  if (st.ok()) h_got.resize(h_tables.size());
+  CANARY_HIP(st, d_tables.download(h_got.data()));
+  if (st.ok()) {
     const auto* table = reinterpret_cast<const amdgpu_canary_xcc_slot*>(h_state.data() + kTableOff);
     const auto* matrix = reinterpret_cast<const amdgpu_canary_pair_slot*>(h_state.data() + kMatrixOff);
     const auto* counters = reinterpret_cast<const unsigned long long*>(h_state.data() + kCountersOff);
@@ -679,14 +661,7 @@ int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inj
     if (slice_xcc_len > 0)
       std::memcpy(slice_xcc_out, sx, sizeof(unsigned int) * (slice_xcc_len < grid ? slice_xcc_len : grid));
   }
-  if (e != hipSuccess) std::snprintf(err, err_len, "fabric check: %s%s", what, hipGetErrorString(e));
-  for (int i = 0; i < 4; ++i)
-    if (ev[i]) (void)hipEventDestroy(ev[i]);
-  if (d_lists) (void)hipFree(d_lists);
-  if (d_tables) (void)hipFree(d_tables);
-  if (d_state) (void)hipFree(d_state);
-  if (d_buf) (void)hipFree(d_buf);
-  return e == hipSuccess ? 0 : -1;
+  return st.report("fabric check: ", err, err_len);
 }
 
 }  // extern "C"

@@ -32,15 +32,13 @@
 #include <cstring>
 #include <vector>
 
-#include "canary_common.h"
+#include "canary_host.h"
 
 namespace {
 
 using namespace canary;
 
 constexpr int kProbeWaves = 4;   // waves per workgroup: one per SIMD of a CU
-constexpr int kMaxBlocks = 4096; // global wave index < 2^14
-constexpr int kMaxLdsBytes = 160 * 1024;
 constexpr int kValuRounds = 48;
 
 // ---- valu chain: the same code on host and device ----------------------------------
@@ -157,11 +155,6 @@ __device__ __forceinline__ uint32_t check_valu(int lane, const uint32_t* __restr
   return valu_digest(s) != expect[lane];
 }
 
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
-  return v;  // lane 0 holds the sum
-}
-
 // counters[0] = waves that moved, counters[1] = their wrong results.  Waves with global
 // index < inject_waves perturb one operand of check `inject_check` (verifier self-test).
 // The dynamic LDS allocation is not used: its size keeps one workgroup per CU.
@@ -176,9 +169,9 @@ __global__ void __launch_bounds__(256) site_probe(int ksteps, int inject_check, 
   const uint32_t key = gw | (seed << 14);
   const bool inject = static_cast<int>(gw) < inject_waves;
   uint32_t bad[kSiteChecks];
-  bad[0] = wave_sum(check_mfma(key, lane, ksteps, inject && inject_check == 0));
-  bad[1] = wave_sum(check_lowp(key, lane, ksteps, inject && inject_check == 1));
-  bad[2] = wave_sum(check_valu(lane, expect, inject && inject_check == 2));
+  bad[0] = wave_total(check_mfma(key, lane, ksteps, inject && inject_check == 0));
+  bad[1] = wave_total(check_lowp(key, lane, ksteps, inject && inject_check == 1));
+  bad[2] = wave_total(check_valu(lane, expect, inject && inject_check == 2));
   const uint32_t site_after = site_id();
   if (lane != 0) return;
   if (wave_site != nullptr && static_cast<int>(gw) < wave_site_len) wave_site[gw] = site;
@@ -191,26 +184,6 @@ __global__ void __launch_bounds__(256) site_probe(int ksteps, int inject_check, 
     atomicAdd(&counters[0], 1u);
     if (bad[0] + bad[1] + bad[2]) atomicAdd(&counters[1], bad[0] + bad[1] + bad[2]);
   }
-}
-
-// One launch with the largest dynamic LDS allocation the device grants (the selection of
-// launch_lds_march in datapath.hip: 160 KB on gfx950); false on a HIP error.
-bool launch_site_probe(const hipDeviceProp_t& prop, int blocks, int ksteps, int inject_check, int inject_waves,
-                       uint32_t seed, const uint32_t* expect, amdgpu_canary_site_slot* table, unsigned int* counters,
-                       unsigned int* wave_site, int wave_site_len) {
-  size_t bytes = prop.maxSharedMemoryPerMultiProcessor > 0 ? prop.maxSharedMemoryPerMultiProcessor : 0;
-  if (bytes > static_cast<size_t>(kMaxLdsBytes)) bytes = kMaxLdsBytes;
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    if (attempt == 1 || bytes == 0) bytes = prop.sharedMemPerBlock;
-    bytes &= ~static_cast<size_t>(1023);
-    if (bytes == 0) return false;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(site_probe), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(bytes));
-    hipLaunchKernelGGL(site_probe, dim3(blocks), dim3(kProbeWaves * kWave), bytes, 0, ksteps, inject_check,
-                       inject_waves, seed, expect, table, counters, wave_site, wave_site_len);
-    if (hipGetLastError() == hipSuccess) return true;
-  }
-  return false;
 }
 
 // Fills the totals and the coverage counts of `r` from a host copy of the table.
@@ -258,77 +231,70 @@ int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, in
   }
   std::vector<amdgpu_canary_site_slot> own_table(table_out ? 0 : kSiteSlots);
   amdgpu_canary_site_slot* table = table_out ? table_out : own_table.data();
+  Status st;
   hipDeviceProp_t prop;
   uint32_t h_expect[kWave];
   unsigned int h_counters[2] = {0, 0};
-  uint32_t* d_expect = nullptr;
-  amdgpu_canary_site_slot* d_table = nullptr;
-  unsigned int *d_counters = nullptr, *d_wave_site = nullptr;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  const size_t table_bytes = sizeof(amdgpu_canary_site_slot) * kSiteSlots;
-  const char* what = "";
+  DeviceBuffer<uint32_t> d_expect;
+  DeviceBuffer<amdgpu_canary_site_slot> d_table;
+  DeviceBuffer<unsigned int> d_counters, d_wave_site;
+  Events<2> ev;
   valu_expected(h_expect);
-  hipError_t e = hipSetDevice(device);
-  if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-  if (e == hipSuccess) e = hipMalloc(&d_expect, sizeof(h_expect));
-  if (e == hipSuccess) e = hipMemcpy(d_expect, h_expect, sizeof(h_expect), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMalloc(&d_table, table_bytes);
-  if (e == hipSuccess) e = hipMemset(d_table, 0, table_bytes);
-  if (e == hipSuccess) e = hipMalloc(&d_counters, sizeof(h_counters));
-  if (e == hipSuccess) e = hipMemset(d_counters, 0, sizeof(h_counters));
-  if (e == hipSuccess && wave_site_len > 0) {
-    e = hipMalloc(&d_wave_site, sizeof(unsigned int) * wave_site_len);
-    if (e == hipSuccess) e = hipMemset(d_wave_site, 0xFF, sizeof(unsigned int) * wave_site_len);
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  CANARY_HIP(st, d_expect.alloc(sizeof(h_expect)));
+  CANARY_HIP(st, d_expect.upload(h_expect));
+  CANARY_HIP(st, d_table.alloc(sizeof(amdgpu_canary_site_slot) * kSiteSlots));
+  CANARY_HIP(st, d_table.zero());
+  CANARY_HIP(st, d_counters.alloc(sizeof(h_counters)));
+  CANARY_HIP(st, d_counters.zero());
+  if (wave_site_len > 0) {
+    CANARY_HIP(st, d_wave_site.alloc(sizeof(unsigned int) * wave_site_len));
+    CANARY_HIP(st, d_wave_site.fill(0xFF));
   }
-  if (e == hipSuccess) e = hipEventCreate(&e0);
-  if (e == hipSuccess) e = hipEventCreate(&e1);
-  if (e == hipSuccess) {
+  CANARY_HIP(st, ev.create());
+  if (st.ok()) {
     out->cus_expected = prop.multiProcessorCount;
     const bool automatic = blocks == 0;
     int grid = automatic ? 2 * prop.multiProcessorCount : blocks;
     if (grid > kMaxBlocks) grid = kMaxBlocks;
     const int max_launches = automatic ? 4 : 1;
-    for (int l = 0; e == hipSuccess && l < max_launches; ++l) {
-      float ms = 0;
-      e = hipEventRecord(e0, 0);
-      if (e == hipSuccess &&
-          !launch_site_probe(prop, grid, ksteps, l == 0 ? inject_check : -1, l == 0 ? inject_waves : 0,
-                             static_cast<uint32_t>(l), d_expect, d_table, d_counters, l == 0 ? d_wave_site : nullptr,
-                             l == 0 ? wave_site_len : 0)) {
-        what = "launch: ";
-        e = hipErrorLaunchFailure;
-      }
-      if (e == hipSuccess) e = hipEventRecord(e1, 0);
-      if (e == hipSuccess) e = hipEventSynchronize(e1);
-      if (e == hipSuccess) e = hipGetLastError();
-      if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-      if (e == hipSuccess) e = hipMemcpy(table, d_table, table_bytes, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) break;
-      out->ms += ms;
+    for (int l = 0; l < max_launches; ++l) {
+      float ms[1] = {0};
+      time_stages(st, ev, ms, [&](int) {
+        if (launch_with_max_lds(site_probe, prop, dim3(grid), dim3(kProbeWaves * kWave), ksteps,
+                                l == 0 ? inject_check : -1, l == 0 ? inject_waves : 0, static_cast<uint32_t>(l),
+                                d_expect.get(), d_table.get(), d_counters.get(),
+                                l == 0 ? d_wave_site.get() : nullptr, l == 0 ? wave_site_len : 0))
+          return hipSuccess;
+        st.stage("launch: ");
+        return hipErrorLaunchFailure;
+      });
+      CANARY_HIP(st, d_table.download(table));
+      if (!st.ok()) break;
+      out->ms += ms[0];
       out->launches = l + 1;
       summarize(table, out);
       if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected) break;
     }
   }
-  if (e == hipSuccess) e = hipMemcpy(h_counters, d_counters, sizeof(h_counters), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && wave_site_len > 0)
-    e = hipMemcpy(wave_site_out, d_wave_site, sizeof(unsigned int) * wave_site_len, hipMemcpyDeviceToHost);
+  CANARY_HIP(st, d_counters.download(h_counters));
+  if (wave_site_len > 0) CANARY_HIP(st, d_wave_site.download(wave_site_out));
   out->moved = h_counters[0];
   out->unlocated_errors = h_counters[1];
-  if (e != hipSuccess) std::snprintf(err, err_len, "site probe: %s%s", what, hipGetErrorString(e));
-  if (e0) (void)hipEventDestroy(e0);
-  if (e1) (void)hipEventDestroy(e1);
-  if (d_wave_site) (void)hipFree(d_wave_site);
-  if (d_counters) (void)hipFree(d_counters);
-  if (d_table) (void)hipFree(d_table);
-  if (d_expect) (void)hipFree(d_expect);
-  return e == hipSuccess ? 0 : -1;
+  return st.report("site probe: ", err, err_len);
 }
 
 // "xcc3/se1/sh0/cu7/simd2" of a packed site
-int amdgpu_canary_format_site(unsigned int site, char* buf, int len) {
-  return std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u/simd%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
-                       (site >> 2) & 0xFu, site & 3u);
-}
+int amdgpu_canary_format_site(unsigned int site, char* buf, int len) { return format_site(site, true, buf, len); }
 
 }  // extern "C"
+
+int canary::sites_describe(const amdgpu_canary_sites_result& r, unsigned long long errors, char* buf, int len) {
+  char where[64] = "an unknown site";  // every wrong wave moved while it ran
+  if (r.n_bad > 0) format_site(r.bad_sites[0], true, where, sizeof(where));
+  int n = std::snprintf(buf, len, "site check: %llu wrong results at %s", errors, where);
+  if (r.n_bad > 1 && n > 0 && n < len)
+    n += std::snprintf(buf + n, len - n, " (+%d more site%s)", r.n_bad - 1, r.n_bad > 2 ? "s" : "");
+  return n;
+}

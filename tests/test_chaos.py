@@ -116,6 +116,7 @@ def test_random_fault_mix_converges(make_cfg, plugin_dir, sock_dir, seed, fixtur
                                     serialised):
     from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import PodResourcesStub
     n = native.load()
+    native.load_bench()  # here, not first in the _Allocator thread: a first-use build would outlast the chaos window
     rng = random.Random(seed)
     be = fixtures.build_backend(fixture)
     be.set_serialised(serialised)

@@ -219,6 +219,19 @@ def test_canary_verifier_catches_injected_corruption():
     assert canary.detects_corruption(0, 64 << 20, 7) == 7
 
 
+def test_hbm_sweep_every_variant_verifies_an_odd_sized_buffer():
+    """All 13 access shapes write and verify 12 305 sixteen-byte words: no multiple of an unroll
+    tile (256 * U, U in 2, 4, 8, 16) nor of the grid, about 48 words per block for the chunked
+    shapes, so every unrolled body, tail, empty block and partial tile runs."""
+    from k8s_gpu_device_plugin_amd.ops import canary
+    rows = canary.hbm_sweep(0, nbytes=(3 * 256 * 16 + 17) * 16, blocks_per_cu=(1,), reps=1)
+    assert [r["variant"] for r in rows] == list(canary.SWEEP_VARIANTS.values()) and len(rows) == 13
+    for r in rows:
+        print("hbm_sweep", r)
+        assert r["rc"] == 0 and r["errors"] == 0, r
+        assert r["write_gbps"] > 0 and r["read_verify_gbps"] > 0, r
+
+
 def test_canary_mfma_verifier_catches_injected_fault():
     """One perturbed bf16 operand in 3 of the exactness blocks must surface as wrong
     accumulator registers; none without injection."""
