@@ -158,6 +158,14 @@ def load():
                                                 ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
                                                 ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_char_p, ctypes.c_int]
         lib.amdgpu_canary_gemm_rate.restype = ctypes.c_int
+        lib.amdgpu_canary_abft.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
+                                           ctypes.c_char_p, ctypes.c_int]
+        lib.amdgpu_canary_abft.restype = ctypes.c_int
+        lib.amdgpu_canary_gemm_tile_map.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_int]
+        lib.amdgpu_canary_gemm_tile_map.restype = ctypes.c_int
         lib.amdgpu_canary_lowp_check.argtypes = [ctypes.c_int] * 5
         lib.amdgpu_canary_lowp_check.restype = ctypes.c_longlong
         lib.amdgpu_canary_lowp_rate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -488,7 +496,27 @@ GEMM_KERNELS = {"auto": 0, "lds128": 1, "pingpong256": 2, "pingpong256s": 3, "pi
                 "pingpong256s_group2": 9, "pingpong256s_group8": 10, "pingpong256s_noprio": 11}
 
 
-def gemm(a_bf16_bits, bt_bf16_bits, device: int = 0, kernel: str = "auto"):
+def _kernel_id(kernel) -> int:
+    """A name of ``GEMM_KERNELS`` or a raw kernel id (the library refuses one it does not know)."""
+    return GEMM_KERNELS[kernel] if isinstance(kernel, str) else int(kernel)
+
+
+def gemm_tile_map(kernel, m: int, n: int):
+    """Tile origin ``(m0, n0)`` of every workgroup of GEMM kernel ``kernel`` at an ``m`` x ``n``
+    product, in workgroup order, from the kernels' own index arithmetic run on the host (no
+    GPU needed): an int32 array [grid, 2].  ``ValueError`` for a shape the kernel refuses."""
+    import numpy as np
+
+    lib = load()
+    grid = lib.amdgpu_canary_gemm_tile_map(_kernel_id(kernel), int(m), int(n), None, None, 0)
+    if grid <= 0:
+        raise ValueError("gemm_tile_map: shape (%d,%d) does not fit kernel %r" % (m, n, kernel))
+    m0, n0 = np.full(grid, -1, dtype=np.int32), np.full(grid, -1, dtype=np.int32)
+    lib.amdgpu_canary_gemm_tile_map(_kernel_id(kernel), int(m), int(n), m0.ctypes.data, n0.ctypes.data, grid)
+    return np.stack([m0, n0], axis=1)
+
+
+def gemm(a_bf16_bits, bt_bf16_bits, device: int = 0, kernel="auto"):
     """C = A @ Bt.T through the LDS-staged MFMA GEMM (the canary's matrix path).
     ``a``: uint16 [M, K] bf16 bit patterns, ``bt``: uint16 [N, K] (B transposed, K
     contiguous); K % 64 == 0 and M, N % 128 == 0 (``lds128``) or % 256 == 0
@@ -504,28 +532,52 @@ def gemm(a_bf16_bits, bt_bf16_bits, device: int = 0, kernel: str = "auto"):
     c = np.empty((m, nn), dtype=np.float32)
     err = ctypes.create_string_buffer(256)
     rc = load().amdgpu_canary_gemm(int(device), a.ctypes.data, bt.ctypes.data, c.ctypes.data, m, nn, k,
-                                   GEMM_KERNELS[kernel], err, 256)
+                                   _kernel_id(kernel), err, 256)
     if rc != 0:
         raise RuntimeError("gemm failed: " + err.value.decode(errors="replace"))
     return c
 
 
 def gemm_rate(device: int = 0, m: int = 4096, n: int = 4096, k: int = 4096, iters: int = 10,
-              inject: bool = False, kernel: str = "auto", random_data: bool = False) -> dict:
-    """Matrix-path canary: timed LDS-staged MFMA GEMMs on exact integer data, then ABFT
-    row/column checksums.  ``errors`` counts rows + columns whose checksum is off.
-    ``random_data``: uniform bf16 operands in [-1, 1) instead (the rate a BLAS benchmark
-    quotes; no checksum, ``errors`` is None)."""
+              inject: bool = False, kernel="auto", random_data: bool = False,
+              skip_verified_launch: bool = False) -> dict:
+    """Matrix-path canary: timed LDS-staged MFMA GEMMs on exact integer data, then one more
+    product written into a poisoned (all-NaN) C, and the ABFT row/column checksums of that
+    one.  ``errors`` counts wrong rows + wrong columns.  ``inject`` corrupts one element of
+    the verified product (2 expected); ``skip_verified_launch`` leaves the poison in place
+    (``m + n`` expected).  ``random_data``: uniform bf16 operands in [-1, 1) instead (the
+    rate a BLAS benchmark quotes; no checksum, ``errors`` is None)."""
     t, e = ctypes.c_double(), ctypes.c_ulonglong()
     err = ctypes.create_string_buffer(256)
-    rc = load().amdgpu_canary_gemm_rate(int(device), m, n, k, iters, int(bool(inject)) | (2 if random_data else 0),
-                                        GEMM_KERNELS[kernel],
-                                        ctypes.byref(t),
-                                        ctypes.byref(e), err, 256)
+    flags = int(bool(inject)) | (2 if random_data else 0) | (4 if skip_verified_launch else 0)
+    rc = load().amdgpu_canary_gemm_rate(int(device), int(m), int(n), int(k), int(iters), flags, _kernel_id(kernel),
+                                        ctypes.byref(t), ctypes.byref(e), err, 256)
     if rc != 0:
         raise RuntimeError("gemm_rate failed: " + err.value.decode(errors="replace"))
     return {"tflops": t.value, "errors": None if random_data else e.value, "shape": (m, n, k), "iters": iters,
             "kernel": kernel, "data": "random" if random_data else "integer"}
+
+
+def abft(a_bf16_bits, bt_bf16_bits, c, device: int = 0) -> tuple:
+    """The matrix path's verifier on its own: the ABFT verdict on a caller-supplied product.
+    ``a``: uint16 [M, K] and ``bt``: uint16 [N, K] bf16 bit patterns of integers, ``c``:
+    float32 [M, N]; any positive M, N and K <= 65536.  Returns ``(row_errors, col_errors)``:
+    the rows and the columns whose checksum is off or that hold an element no healthy product
+    holds (a fraction, a magnitude above 2^24, NaN, -0)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(a_bf16_bits, dtype=np.uint16)
+    bt = np.ascontiguousarray(bt_bf16_bits, dtype=np.uint16)
+    c = np.ascontiguousarray(c, dtype=np.float32)
+    if a.ndim != 2 or bt.ndim != 2 or a.shape[1] != bt.shape[1] or c.shape != (a.shape[0], bt.shape[0]):
+        raise ValueError("shapes do not match: A %s, Bt %s, C %s" % (a.shape, bt.shape, c.shape))
+    rows, cols = ctypes.c_ulonglong(), ctypes.c_ulonglong()
+    err = ctypes.create_string_buffer(256)
+    rc = load().amdgpu_canary_abft(int(device), a.ctypes.data, bt.ctypes.data, c.ctypes.data, a.shape[0], bt.shape[0],
+                                   a.shape[1], ctypes.byref(rows), ctypes.byref(cols), err, 256)
+    if rc != 0:
+        raise RuntimeError("abft failed: " + err.value.decode(errors="replace"))
+    return int(rows.value), int(cols.value)
 
 
 def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0, passes: int = 1) -> dict:

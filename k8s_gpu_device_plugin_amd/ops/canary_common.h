@@ -191,6 +191,14 @@ struct amdgpu_canary_datapath_result {  // datapath.hip; no ctypes mirror
 int amdgpu_canary_datapaths(int device, int iters, amdgpu_canary_datapath_result* out, char* err, int err_len);
 int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flags, int kernel, double* tflops,
                             unsigned long long* errors, char* err, int err_len);
+// flags of amdgpu_canary_gemm_rate
+constexpr int kGemmInject = 1, kGemmRandomData = 2, kGemmSkipVerifiedLaunch = 4;
+// the ABFT verdict on a caller-supplied C (any positive M, N; 0 < K <= 65536): wrong rows, wrong columns
+int amdgpu_canary_abft(int device, const unsigned short* a_host, const unsigned short* bt_host, const float* c_host,
+                       int M, int N, int K, unsigned long long* row_errors, unsigned long long* col_errors, char* err,
+                       int err_len);
+// host only: the grid of GEMM kernel id `kernel` at M x N (0: refused) and each workgroup's tile origin
+int amdgpu_canary_gemm_tile_map(int kernel, int M, int N, int* m0_out, int* n0_out, int len);
 
 constexpr int kSiteChecks = 3;  // 0 mfma, 1 lowp, 2 valu
 

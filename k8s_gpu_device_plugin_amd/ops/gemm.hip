@@ -58,9 +58,20 @@ constexpr int kTileM = 128, kTileN = 128, kTileK = 64;
 constexpr int kTileBytes = kTileM * kTileK * 2;  // one operand tile, 16 KiB
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
-__device__ __forceinline__ int xcd_remap(int orig, int nwg) {  // bijective for any nwg
+// The index maps below are host + device: the kernels pass blockIdx.x and gridDim.x, and
+// amdgpu_canary_gemm_tile_map walks the same arithmetic on the host (tests/test_canary_gemm.py
+// checks that every grid is a permutation of its tile set).
+__host__ __device__ __forceinline__ int xcd_remap(int orig, int nwg) {  // bijective for any nwg
   const int xcd = orig % 8, q = nwg / 8, r = nwg % 8;
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + orig / 8;
+}
+
+// Output tile of workgroup `block` of `nblocks` in gemm_lds: XCD-aware remap, then row-major tiles.
+__host__ __device__ __forceinline__ void tile_origin128(int block, int nblocks, int M, int N, int* m0, int* n0) {
+  const int nbn = N / kTileN;
+  const int wg = xcd_remap(block, nblocks);
+  *m0 = (wg / nbn) * kTileM;
+  *n0 = (wg % nbn) * kTileN;
 }
 
 __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, const short* __restrict__ Bt,
@@ -68,9 +79,8 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
   // one __shared__ array for everything (a second object can de-pipeline glds waits)
   __shared__ __attribute__((aligned(16))) char smem[2 * 2 * kTileBytes];  // [buf][A|B][128][64] bf16
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int nbn = N / kTileN;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
-  const int m0 = (wg / nbn) * kTileM, n0 = (wg % nbn) * kTileN;
+  int m0, n0;
+  tile_origin128(blockIdx.x, gridDim.x, M, N, &m0, &n0);
   if (m0 + kTileM > M || n0 + kTileN > N) return;  // host checks shapes
   const int wr = wave >> 1, wc = wave & 1;
   const int r = lane & 31, h = lane >> 5;
@@ -162,16 +172,20 @@ constexpr int kBOp = kBT * kBK * 2;  // one operand tile, 32 KiB
 constexpr int kBStage = 2 * kBOp;    // A + B of one K-tile, 64 KiB
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-// Output tile of this workgroup: XCD-aware bijective remap, then tiles rastered in groups
-// of `group` tile rows so one XCD's consecutive workgroups share A and B panels in L2.
-__device__ __forceinline__ void tile_origin256(int M, int N, int group, int* m0, int* n0) {
+// Output tile of workgroup `block` of `nblocks`: XCD-aware bijective remap, then tiles rastered
+// in groups of `group` tile rows so one XCD's consecutive workgroups share A and B panels in L2.
+__host__ __device__ __forceinline__ void tile_origin256(int block, int nblocks, int M, int N, int group, int* m0,
+                                                        int* n0) {
   const int nbm = M / kBT, nbn = N / kBT;
-  const int wg = xcd_remap(blockIdx.x, gridDim.x);
+  const int wg = xcd_remap(block, nblocks);
   const int per_group = group * nbn, first_m = (wg / per_group) * group;
   const int gm = nbm - first_m < group ? nbm - first_m : group;
   *m0 = (first_m + (wg % per_group) % gm) * kBT;
   *n0 = ((wg % per_group) / gm) * kBT;
 }
+
+// Tile rows per raster group of kernel id `kind` (2-11, see pick_gemm): gemm256s's kGroupM.
+constexpr int gemm_group(int kind) { return kind == 9 ? 2 : kind == 10 ? 8 : 4; }
 
 __device__ __forceinline__ void section_end() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this section's LDS reads are done
@@ -185,7 +199,7 @@ __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, cons
   __shared__ __attribute__((aligned(16))) char smem[2 * kBStage];  // the only LDS object
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int m0, n0;
-  tile_origin256(M, N, 4, &m0, &n0);
+  tile_origin256(blockIdx.x, gridDim.x, M, N, gemm_group(2), &m0, &n0);
   if (m0 + kBT > M || n0 + kBT > N) return;  // host checks shapes (block-uniform exit)
   const int wr = wave >> 2, wc = wave & 3;
   const bool g1 = wr == 1;
@@ -314,7 +328,7 @@ __global__ void __launch_bounds__(512) gemm256s(const short* __restrict__ A, con
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = kScalarWave ? __builtin_amdgcn_readfirstlane(tid >> 6) : tid >> 6;
   int m0, n0;
-  tile_origin256(M, N, kGroupM, &m0, &n0);
+  tile_origin256(blockIdx.x, gridDim.x, M, N, kGroupM, &m0, &n0);
   if (m0 + kBT > M || n0 + kBT > N) return;  // host checks shapes (block-uniform exit)
   const int wr = wave >> 2, wc = wave & 3;
   const bool g1 = wr == 1;
@@ -498,31 +512,53 @@ __global__ void __launch_bounds__(256) gemm_colsum(const short* __restrict__ X, 
   atomicAdd(reinterpret_cast<unsigned long long*>(out + k), static_cast<unsigned long long>(s));
 }
 
+// An element of a healthy product is an integer of magnitude <= 2^24 and never -0: the
+// accumulators start at +0, and under round-to-nearest +0 + -0 and a + -a both give +0.
+// Decided on the bit pattern, so NaN, Inf and denormals need no floating-point compare and a
+// fraction below the units place cannot hide behind the cast to an integer.
+__device__ __forceinline__ bool abft_healthy(float v) {
+  uint32_t u;
+  __builtin_memcpy(&u, &v, 4);
+  const uint32_t mag = u & 0x7fffffffu;
+  if (mag == 0) return u == 0;                        // +0, not -0
+  if (mag < 0x3f800000u || mag > 0x4b800000u) return false;  // 0 < |v| < 1; |v| > 2^24, Inf, NaN
+  const int frac_bits = 150 - static_cast<int>(mag >> 23);  // mantissa bits below the units place
+  return frac_bits <= 0 || (mag & ((1u << frac_bits) - 1u)) == 0;
+}
+
 // ABFT: for row i, sum_n C[i][n] must equal sum_k A[i][k] * (sum_n Bt[n][k]); for column
 // n, sum_m C[m][n] must equal sum_k (sum_m A[m][k]) * Bt[n][k].  One block per row /
-// column, int64 reductions (C holds exact integers).  mode 0 = rows, 1 = columns.
+// column, int64 reductions (C holds exact integers).  mode 0 = rows, 1 = columns; a row or
+// column is wrong when its checksum is off or it holds an element that is not healthy
+// (those stay out of the sum), and adds 1 to errors[mode].
 __global__ void __launch_bounds__(256) gemm_abft(const short* __restrict__ X, const float* __restrict__ C,
                                                  const long long* __restrict__ other_sum, int M, int N, int K,
                                                  int mode, unsigned long long* __restrict__ errors) {
-  __shared__ long long red[2][256];
+  __shared__ long long red[3][256];
   const int idx = blockIdx.x, tid = threadIdx.x;
-  long long expect = 0, got = 0;
+  long long expect = 0, got = 0, bad = 0;
   for (int k = tid; k < K; k += 256) expect += static_cast<long long>(bf16_to_int(X[static_cast<size_t>(idx) * K + k])) * other_sum[k];
-  if (mode == 0)
-    for (int n = tid; n < N; n += 256) got += static_cast<long long>(C[static_cast<size_t>(idx) * N + n]);
-  else
-    for (int m = tid; m < M; m += 256) got += static_cast<long long>(C[static_cast<size_t>(m) * N + idx]);
+  const int n_el = mode == 0 ? N : M;
+  for (int e = tid; e < n_el; e += 256) {
+    const float v = mode == 0 ? C[static_cast<size_t>(idx) * N + e] : C[static_cast<size_t>(e) * N + idx];
+    if (abft_healthy(v))
+      got += static_cast<long long>(v);
+    else
+      ++bad;
+  }
   red[0][tid] = expect;
   red[1][tid] = got;
+  red[2][tid] = bad;
   __syncthreads();
   for (int s = 128; s > 0; s >>= 1) {
     if (tid < s) {
       red[0][tid] += red[0][tid + s];
       red[1][tid] += red[1][tid + s];
+      red[2][tid] += red[2][tid + s];
     }
     __syncthreads();
   }
-  if (tid == 0 && red[0][0] != red[1][0]) atomicAdd(errors, 1ull);
+  if (tid == 0 && (red[0][0] != red[1][0] || red[2][0] != 0)) atomicAdd(errors + mode, 1ull);
 }
 
 // GEMM kernel choice: 1 = gemm_lds (128x128 tiles), 2 = gemm256 (256x256 tiles, wave-group
@@ -554,9 +590,9 @@ void launch_gemm(int kind, const short* a, const short* b, float* c, int M, int 
   else if (kind == 8)
     hipLaunchKernelGGL((gemm256s<4, false, false>), g256, b256, 0, 0, a, b, c, M, N, K);
   else if (kind == 9)
-    hipLaunchKernelGGL((gemm256s<4, false, true, 2>), g256, b256, 0, 0, a, b, c, M, N, K);
+    hipLaunchKernelGGL((gemm256s<4, false, true, gemm_group(9)>), g256, b256, 0, 0, a, b, c, M, N, K);
   else if (kind == 10)
-    hipLaunchKernelGGL((gemm256s<4, false, true, 8>), g256, b256, 0, 0, a, b, c, M, N, K);
+    hipLaunchKernelGGL((gemm256s<4, false, true, gemm_group(10)>), g256, b256, 0, 0, a, b, c, M, N, K);
   else if (kind == 11)
     hipLaunchKernelGGL((gemm256s<4, false, true, 4, false>), g256, b256, 0, 0, a, b, c, M, N, K);
   else if (kind == 2)
@@ -587,9 +623,77 @@ int gemm_on_host_data(int device, const unsigned short* a_host, size_t a_bytes, 
   return st.report("", err, err_len);
 }
 
+// The checksum sequence: the column sums of A and of Bt, then the row and the column verdicts
+// on C.  asum and bsum hold K sums each; counts[0] += wrong rows, counts[1] += wrong columns
+// (the caller zeroes counts).  Shape-generic: any positive M, N, K.
+void abft_checksums(Status& st, const short* a, const short* bt, const float* c, DeviceBuffer<long long>& asum,
+                    DeviceBuffer<long long>& bsum, unsigned long long* counts, int M, int N, int K) {
+  CANARY_HIP(st, asum.zero());
+  CANARY_HIP(st, bsum.zero());
+  if (!st.ok()) return;
+  const int kb = (K + 255) / 256;
+  hipLaunchKernelGGL(gemm_colsum, dim3(kb, (M + kSlab - 1) / kSlab), dim3(256), 0, 0, a, M, K, asum.get());
+  hipLaunchKernelGGL(gemm_colsum, dim3(kb, (N + kSlab - 1) / kSlab), dim3(256), 0, 0, bt, N, K, bsum.get());
+  hipLaunchKernelGGL(gemm_abft, dim3(M), dim3(256), 0, 0, a, c, bsum.get(), M, N, K, 0, counts);
+  hipLaunchKernelGGL(gemm_abft, dim3(N), dim3(256), 0, 0, bt, c, asum.get(), M, N, K, 1, counts);
+  st.check(hipGetLastError());
+}
+
 }  // namespace
 
 extern "C" {
+
+// Tile origin of every workgroup of kernel id `kernel` at shape M x N, on the host (no GPU
+// needed): returns the grid size and fills the first min(len, grid) entries of m0_out / n0_out
+// with the kernel's own index arithmetic; 0 if pick_gemm refuses the shape or the id.
+int amdgpu_canary_gemm_tile_map(int kernel, int M, int N, int* m0_out, int* n0_out, int len) {
+  const int kind = pick_gemm(M, N, kTileK, kernel);
+  if (kind == 0) return 0;
+  const int grid = kind == 1 ? (M / kTileM) * (N / kTileN) : (M / kBT) * (N / kBT);
+  for (int b = 0; b < grid && b < len; ++b) {
+    if (kind == 1)
+      tile_origin128(b, grid, M, N, &m0_out[b], &n0_out[b]);
+    else
+      tile_origin256(b, grid, M, N, gemm_group(kind), &m0_out[b], &n0_out[b]);
+  }
+  return grid;
+}
+
+// The ABFT verdict on a caller-supplied C: uploads A [MxK], Bt [NxK] (bf16 bit patterns) and
+// C [MxN], runs the checksum sequence and returns the wrong rows and the wrong columns.
+int amdgpu_canary_abft(int device, const unsigned short* a_host, const unsigned short* bt_host, const float* c_host,
+                       int M, int N, int K, unsigned long long* row_errors, unsigned long long* col_errors, char* err,
+                       int err_len) {
+  *row_errors = 0;
+  *col_errors = 0;
+  if (M <= 0 || N <= 0 || K <= 0 || K > 65536) {
+    std::snprintf(err, err_len, "abft shape (%d,%d,%d) must be positive with K <= 65536", M, N, K);
+    return -1;
+  }
+  Status st;
+  DeviceBuffer<short> a, b;
+  DeviceBuffer<float> c;
+  DeviceBuffer<long long> asum, bsum;
+  DeviceBuffer<unsigned long long> d_err;
+  unsigned long long counts[2] = {0, 0};
+  CANARY_HIP(st, hipSetDevice(device));
+  CANARY_HIP(st, a.alloc(static_cast<size_t>(M) * K * 2));
+  CANARY_HIP(st, b.alloc(static_cast<size_t>(N) * K * 2));
+  CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
+  CANARY_HIP(st, asum.alloc(static_cast<size_t>(K) * 8));
+  CANARY_HIP(st, bsum.alloc(static_cast<size_t>(K) * 8));
+  CANARY_HIP(st, d_err.alloc(sizeof(counts)));
+  CANARY_HIP(st, d_err.zero());
+  CANARY_HIP(st, a.upload(a_host));
+  CANARY_HIP(st, b.upload(bt_host));
+  CANARY_HIP(st, c.upload(c_host));
+  abft_checksums(st, a.get(), b.get(), c.get(), asum, bsum, d_err.get(), M, N, K);
+  CANARY_HIP(st, hipDeviceSynchronize());
+  CANARY_HIP(st, d_err.download(counts));
+  *row_errors = counts[0];
+  *col_errors = counts[1];
+  return st.report("", err, err_len);
+}
 
 // Host wrapper for the numerics test: inputs/outputs in host memory.
 int amdgpu_canary_mfma_gemm(int device, const unsigned short* a_host, const unsigned short* b_host, float* c_host,
@@ -619,21 +723,27 @@ int amdgpu_canary_gemm(int device, const unsigned short* a_host, const unsigned 
                            [&](const short* a, const short* b, float* c) { launch_gemm(kind, a, b, c, M, N, K); });
 }
 
-// Matrix-path canary: device-generated integer operands, `iters` timed GEMMs, then the
-// ABFT row + column checksums of the result.  *tflops = dense bf16 rate achieved,
-// *errors = rows + columns whose checksum is off (0 on a healthy partition).
+// Matrix-path canary: device-generated integer operands, `iters` timed GEMMs, then C is
+// poisoned (every byte 0xFF: NaN) and one more, untimed GEMM writes the product that the ABFT
+// row + column checksums verify, so a tile a launch leaves unwritten cannot hide behind an
+// earlier launch's data.  *tflops = dense bf16 rate achieved, *errors = wrong rows + wrong
+// columns (0 on a healthy partition).
 // flags bit 0 corrupts one element of C before the check (verifier self-test); bit 1
 // fills the operands with random bf16 in [-1, 1) instead and skips the (then inexact)
-// checksums: the rate on full-mantissa data, comparable with a BLAS benchmark.
+// checksums: the rate on full-mantissa data, comparable with a BLAS benchmark; bit 2 skips
+// the launch after the poison, so every row and every column must be reported (M + N).
 int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flags, int kernel, double* tflops,
                             unsigned long long* errors, char* err, int err_len) {
-  const bool inject = flags & 1, random_data = flags & 2;
+  const bool inject = flags & kGemmInject, random_data = flags & kGemmRandomData,
+             skip_verified_launch = flags & kGemmSkipVerifiedLaunch;
   *tflops = 0;
   *errors = 0;
   const int kind = pick_gemm(M, N, K, kernel);
   if (kind == 0 || K > 65536 || iters < 1) {
-    std::snprintf(err, err_len, "shape (%d,%d,%d) does not fit kernel %d (M,N %% 128 or 256, K %% 64, K <= 65536)",
-                  M, N, K, kernel);
+    std::snprintf(err, err_len,
+                  "shape (%d,%d,%d) x %d iters does not fit kernel %d (M,N %% 128 or 256, K %% 64, K <= 65536, "
+                  "iters >= 1)",
+                  M, N, K, iters, kernel);
     return -1;
   }
   Status st;
@@ -649,7 +759,8 @@ int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flag
   CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
   CANARY_HIP(st, asum.alloc(static_cast<size_t>(K) * 8));
   CANARY_HIP(st, bsum.alloc(static_cast<size_t>(K) * 8));
-  CANARY_HIP(st, d_err.alloc(8));
+  unsigned long long counts[2] = {0, 0};
+  CANARY_HIP(st, d_err.alloc(sizeof(counts)));
   CANARY_HIP(st, d_err.zero());
   CANARY_HIP(st, ev.create());
   if (st.ok()) {
@@ -667,25 +778,21 @@ int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flag
     for (int i = 0; i < iters; ++i) launch_gemm(kind, a.get(), b.get(), c.get(), M, N, K);
     return hipSuccess;
   });
+  if (!random_data) {
+    CANARY_HIP(st, c.fill(0xFF));  // the poison: what is verified below was written after it
+    if (st.ok() && !skip_verified_launch) {
+      launch_gemm(kind, a.get(), b.get(), c.get(), M, N, K);
+      st.check(hipGetLastError());
+    }
+  }
   if (inject) {
     const float junk = 12345.0f;
     CANARY_HIP(st, hipMemcpy(c.get() + static_cast<size_t>(M / 2) * N + N / 3, &junk, 4, hipMemcpyHostToDevice));
   }
-  if (!random_data) {
-    CANARY_HIP(st, asum.zero());
-    CANARY_HIP(st, bsum.zero());
-    if (st.ok()) {
-      hipLaunchKernelGGL(gemm_colsum, dim3((K + 255) / 256, (M + kSlab - 1) / kSlab), dim3(256), 0, 0, a.get(), M, K,
-                         asum.get());
-      hipLaunchKernelGGL(gemm_colsum, dim3((K + 255) / 256, (N + kSlab - 1) / kSlab), dim3(256), 0, 0, b.get(), N, K,
-                         bsum.get());
-      hipLaunchKernelGGL(gemm_abft, dim3(M), dim3(256), 0, 0, a.get(), c.get(), bsum.get(), M, N, K, 0, d_err.get());
-      hipLaunchKernelGGL(gemm_abft, dim3(N), dim3(256), 0, 0, b.get(), c.get(), asum.get(), M, N, K, 1, d_err.get());
-      st.check(hipGetLastError());
-    }
-  }
+  if (!random_data) abft_checksums(st, a.get(), b.get(), c.get(), asum, bsum, d_err.get(), M, N, K);
   CANARY_HIP(st, hipDeviceSynchronize());
-  CANARY_HIP(st, d_err.download(errors));
+  CANARY_HIP(st, d_err.download(counts));
+  *errors = counts[0] + counts[1];
   if (st.ok() && ms[0] > 0) *tflops = 2.0 * M * N * K * iters / (ms[0] * 1e-3) / 1e12;
   return st.report("", err, err_len);
 }

@@ -13,6 +13,7 @@ from k8s_gpu_device_plugin_amd import _build
 from k8s_gpu_device_plugin_amd.ops import canary
 
 EXPORTS = """
+amdgpu_canary_abft amdgpu_canary_gemm_tile_map
 amdgpu_canary_atomic_expected amdgpu_canary_atomic_op_name amdgpu_canary_cu amdgpu_canary_cu_describe
 amdgpu_canary_cu_regs amdgpu_canary_cu_sizeof amdgpu_canary_datapaths amdgpu_canary_detects_corruption
 amdgpu_canary_device_count amdgpu_canary_fabric amdgpu_canary_fabric_describe amdgpu_canary_format_site
