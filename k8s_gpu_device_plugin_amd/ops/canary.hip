@@ -51,8 +51,7 @@ __global__ void __launch_bounds__(64) mfma_exact(int ksteps, int inject_blocks,
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
   const uint32_t blk = blockIdx.x;
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int s = 0; s < ksteps; ++s) {
     bf16x8 a, b;
     for (int j = 0; j < 8; ++j) {
@@ -66,7 +65,7 @@ __global__ void __launch_bounds__(64) mfma_exact(int ksteps, int inject_blocks,
   uint32_t bad = 0;
   const int col = lane & 31;
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);  // C/D map of 32x32x16
+    const int row = cd_row32(reg, h);
     int ref = 0;
     for (int k = 0; k < ksteps * 16; ++k) ref += a_val(blk, row, k) * b_val(blk, k, col);
     bad += acc[reg] != static_cast<float>(ref);
@@ -83,8 +82,7 @@ __global__ void __launch_bounds__(256) mfma_rate(int iters, float* __restrict__ 
     a[j] = bf16_of_int(((lane + j) % 5) - 2);
     b[j] = bf16_of_int(((lane * 3 + j) % 7) - 3);
   }
-  f32x16 acc0, acc1;
-  for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
+  f32x16 acc0 = zero_f32x16(), acc1 = zero_f32x16();
   for (int it = 0; it < iters; ++it) {
     acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc0, 0, 0, 0);
     acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, acc1, 0, 0, 0);

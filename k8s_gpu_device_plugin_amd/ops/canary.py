@@ -471,16 +471,27 @@ def hbm_sweep(device: int = 0, nbytes: int = 4 << 30, variants=tuple(SWEEP_VARIA
     return rows
 
 
+def _bf16_operands(a_bits, b_bits, b_k_axis: int, error: str = None):
+    """Two bf16 operands as contiguous uint16 arrays, A [M, K] and B with K on axis ``b_k_axis``:
+    ``(a, b, m, n, k)``.  ``ValueError`` (with ``error`` as its text, if given) unless both are
+    2-D and agree on K."""
+    import numpy as np
+
+    a, b = (np.ascontiguousarray(x, dtype=np.uint16) for x in (a_bits, b_bits))
+    if error and (a.ndim != 2 or b.ndim != 2):
+        raise ValueError(error)
+    (m, k), (n, k2) = a.shape, b.shape[::1 if b_k_axis else -1]
+    if k != k2:
+        raise ValueError(error or "inner dimensions differ: %d vs %d" % (k, k2))
+    return a, b, m, n, k
+
+
 def mfma_gemm(a_bf16_bits, b_bf16_bits, device: int = 0):
     """C = A @ B through the canary's MFMA kernel.  ``a``/``b``: uint16 numpy arrays of
     bf16 bit patterns (row-major, M,N % 32 == 0, K % 16 == 0); returns float32 [M, N]."""
     import numpy as np
 
-    a = np.ascontiguousarray(a_bf16_bits, dtype=np.uint16)
-    b = np.ascontiguousarray(b_bf16_bits, dtype=np.uint16)
-    (m, k), (k2, nn) = a.shape, b.shape
-    if k != k2:
-        raise ValueError("inner dimensions differ: %d vs %d" % (k, k2))
+    a, b, m, nn, k = _bf16_operands(a_bf16_bits, b_bf16_bits, 0)
     c = np.empty((m, nn), dtype=np.float32)
     err = ctypes.create_string_buffer(256)
     rc = load().amdgpu_canary_mfma_gemm(int(device), a.ctypes.data, b.ctypes.data, c.ctypes.data, m, nn, k, err, 256)
@@ -494,6 +505,8 @@ def mfma_gemm(a_bf16_bits, b_bf16_bits, device: int = 0):
 GEMM_KERNELS = {"auto": 0, "lds128": 1, "pingpong256": 2, "pingpong256s": 3, "pingpong256s_b2": 4,
                 "pingpong256s_b0": 5, "pingpong256s_b3": 6, "pingpong256s_g1early": 7, "pingpong256s_vwave": 8,
                 "pingpong256s_group2": 9, "pingpong256s_group8": 10, "pingpong256s_noprio": 11}
+# flags of amdgpu_canary_gemm_rate, as in canary_common.h
+GEMM_INJECT, GEMM_RANDOM_DATA, GEMM_SKIP_VERIFIED_LAUNCH = 1, 2, 4
 
 
 def _kernel_id(kernel) -> int:
@@ -524,11 +537,7 @@ def gemm(a_bf16_bits, bt_bf16_bits, device: int = 0, kernel="auto"):
     [M, N]."""
     import numpy as np
 
-    a = np.ascontiguousarray(a_bf16_bits, dtype=np.uint16)
-    bt = np.ascontiguousarray(bt_bf16_bits, dtype=np.uint16)
-    (m, k), (nn, k2) = a.shape, bt.shape
-    if k != k2:
-        raise ValueError("inner dimensions differ: %d vs %d" % (k, k2))
+    a, bt, m, nn, k = _bf16_operands(a_bf16_bits, bt_bf16_bits, 1)
     c = np.empty((m, nn), dtype=np.float32)
     err = ctypes.create_string_buffer(256)
     rc = load().amdgpu_canary_gemm(int(device), a.ctypes.data, bt.ctypes.data, c.ctypes.data, m, nn, k,
@@ -549,7 +558,8 @@ def gemm_rate(device: int = 0, m: int = 4096, n: int = 4096, k: int = 4096, iter
     rate a BLAS benchmark quotes; no checksum, ``errors`` is None)."""
     t, e = ctypes.c_double(), ctypes.c_ulonglong()
     err = ctypes.create_string_buffer(256)
-    flags = int(bool(inject)) | (2 if random_data else 0) | (4 if skip_verified_launch else 0)
+    flags = ((GEMM_INJECT if inject else 0) | (GEMM_RANDOM_DATA if random_data else 0) |
+             (GEMM_SKIP_VERIFIED_LAUNCH if skip_verified_launch else 0))
     rc = load().amdgpu_canary_gemm_rate(int(device), int(m), int(n), int(k), int(iters), flags, _kernel_id(kernel),
                                         ctypes.byref(t), ctypes.byref(e), err, 256)
     if rc != 0:
@@ -566,15 +576,15 @@ def abft(a_bf16_bits, bt_bf16_bits, c, device: int = 0) -> tuple:
     holds (a fraction, a magnitude above 2^24, NaN, -0)."""
     import numpy as np
 
-    a = np.ascontiguousarray(a_bf16_bits, dtype=np.uint16)
-    bt = np.ascontiguousarray(bt_bf16_bits, dtype=np.uint16)
     c = np.ascontiguousarray(c, dtype=np.float32)
-    if a.ndim != 2 or bt.ndim != 2 or a.shape[1] != bt.shape[1] or c.shape != (a.shape[0], bt.shape[0]):
-        raise ValueError("shapes do not match: A %s, Bt %s, C %s" % (a.shape, bt.shape, c.shape))
+    mismatch = "shapes do not match: A %s, Bt %s, C %s" % (np.shape(a_bf16_bits), np.shape(bt_bf16_bits), c.shape)
+    a, bt, m, n, k = _bf16_operands(a_bf16_bits, bt_bf16_bits, 1, mismatch)
+    if c.shape != (m, n):
+        raise ValueError(mismatch)
     rows, cols = ctypes.c_ulonglong(), ctypes.c_ulonglong()
     err = ctypes.create_string_buffer(256)
-    rc = load().amdgpu_canary_abft(int(device), a.ctypes.data, bt.ctypes.data, c.ctypes.data, a.shape[0], bt.shape[0],
-                                   a.shape[1], ctypes.byref(rows), ctypes.byref(cols), err, 256)
+    rc = load().amdgpu_canary_abft(int(device), a.ctypes.data, bt.ctypes.data, c.ctypes.data, m, n, k,
+                                   ctypes.byref(rows), ctypes.byref(cols), err, 256)
     if rc != 0:
         raise RuntimeError("abft failed: " + err.value.decode(errors="replace"))
     return int(rows.value), int(cols.value)

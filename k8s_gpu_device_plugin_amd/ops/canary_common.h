@@ -1,7 +1,7 @@
 // Shared by every gfx950 canary source (canary.hip, hbm.hip, gemm.hip, datapath.hip,
 // sites.hip, fabric.hip, cumem.hip).  Device side: the hash that derives exact small-integer
-// operands, the MFMA register vector types, the bf16 / OCP low-precision operand packing,
-// the s_getreg immediates, site_id(), the wave and block error reductions.  And the C ABI,
+// operands, the MFMA register vector types and the 32x32 C/D row map, the bf16 / OCP
+// low-precision operand packing, the s_getreg immediates, site_id(), the wave and block error reductions.  And the C ABI,
 // declared here once: every result struct that canary.py mirrors with ctypes, with its size
 // pinned, and the prototype of every exported entry point that another source calls.  The
 // host-side helpers are in canary_host.h.
@@ -16,6 +16,19 @@ constexpr int kWave = 64;
 constexpr int kMaxBlocks = 4096;  // grid cap of the located checks: the index of a wave of 4-wave workgroups < 2^14
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
+
+// C/D map of the 32x32 MFMA forms (cdna_hip_programming.md §3; it does not depend on the
+// operand type): accumulator register `reg` (0-15) of a lane in half h = lane >> 5 is the
+// element of this row in column lane & 31.
+__device__ __forceinline__ int cd_row32(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
+
+// A zeroed accumulator.  lowp_rate and lowp_gemm (datapath.hip) spell the loop out instead:
+// with the call the compiler schedules or allocates those two differently (as with wave_sum below).
+__device__ __forceinline__ f32x16 zero_f32x16() {
+  f32x16 v;
+  for (int i = 0; i < 16; ++i) v[i] = 0.f;
+  return v;
+}
 
 // s_getreg_b32 immediate: register id 5:0, bit offset 10:6, size - 1 15:11
 constexpr int kHwRegHwId = 4, kHwRegXccId = 20;

@@ -27,8 +27,8 @@
 //   * fp4:     element j is k = 32 h + j (the lane's 32 elements are its own block);
 //   * fp8/bf8: element j is k = 32 (j >> 4) + 16 h + (j & 15), i.e. two K=32 halves, each
 //     in the 32x32x16 map, so block h spans elements 16h..16h+15 of BOTH lane halves.
-// A and B use the same map, C/D the dtype-independent 32x32 one (cdna_hip_programming.md
-// §3).  tests/test_gpu_datapath.py checks it against a PyTorch fp32 GEMM on random codes
+// A and B use the same map, C/D the dtype-independent 32x32 one (cd_row32 in
+// canary_common.h).  tests/test_gpu_datapath.py checks it against a PyTorch fp32 GEMM on random codes
 // and random block scales, which only matches if both maps are right.
 //
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
@@ -50,8 +50,7 @@ __global__ void __launch_bounds__(64) lowp_exact(int ksteps, int vary_scale, int
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
   const uint32_t blk = blockIdx.x + (static_cast<uint32_t>(FMT + 1) << 20);  // distinct data per format
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int s = 0; s < ksteps; ++s) {
     i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -69,7 +68,7 @@ __global__ void __launch_bounds__(64) lowp_exact(int ksteps, int vary_scale, int
   uint32_t bad = 0;
   const int col = lane & 31;
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int row = cd_row32(reg, h);
     int ref = 0;
     for (int kb = 0; kb < 2 * ksteps; ++kb) {
       int part = 0;
@@ -88,8 +87,7 @@ __global__ void __launch_bounds__(64) fp8_exact(int ksteps, int inject_blocks, u
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
   const uint32_t blk = blockIdx.x + (0x77u << 20);
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int s = 0; s < ksteps; ++s) {
     uint64_t a = 0, b = 0;
 #pragma unroll
@@ -105,7 +103,7 @@ __global__ void __launch_bounds__(64) fp8_exact(int ksteps, int inject_blocks, u
   uint32_t bad = 0;
   const int col = lane & 31;
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int row = cd_row32(reg, h);
     int ref = 0;
     for (int k = 0; k < ksteps * 16; ++k) ref += a_val(blk, row, k) * b_val(blk, k, col);
     bad += acc[reg] != static_cast<float>(ref);
@@ -162,7 +160,7 @@ __global__ void __launch_bounds__(64) lowp_gemm(const uint8_t* __restrict__ A, c
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, FMT, FMT, 0, ka, 0, kb);
   }
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int row = cd_row32(reg, h);
     C[static_cast<size_t>(m0 + row) * N + n0 + (lane & 31)] = acc[reg];
   }
 }
@@ -181,11 +179,10 @@ __global__ void __launch_bounds__(64) lowp_raw(const uint8_t* __restrict__ a, co
     put<FMT>(x, j, a[lane * 32 + j] & (FMT == kFp4 ? 0xFu : 0xFFu));
     put<FMT>(y, j, b[lane * 32 + j] & (FMT == kFp4 ? 0xFu : 0xFFu));
   }
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x, y, acc, FMT, FMT, 0, sa[lane], 0, sb[lane]);
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5);
+    const int row = cd_row32(reg, lane >> 5);
     C[row * 32 + (lane & 31)] = acc[reg];
   }
 }

@@ -2,7 +2,7 @@
 //
 // Three GEMMs on v_mfma_f32_*_bf16 (a plain one-wave-per-tile kernel for the numerics test,
 // the LDS-staged 128x128 kernel, and the 256x256 ping-pong kernel with its measured
-// variants, kernel ids 0-11 in pick_gemm), the operand fills, and the ABFT row / column
+// variants, kernel ids 1-11 in kGemmVariants), the operand fills, and the ABFT row / column
 // checksums that verify a whole product of exact integer data.
 //
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
@@ -21,15 +21,14 @@ using namespace canary;
 // row-major).  One wave per 32x32 output tile, K stepped 16 at a time through
 // v_mfma_f32_32x32x16_bf16 with the gfx950 operand maps: lane l (r = l&31, h = l>>5)
 // feeds A[r][k0+8h+j] and B[k0+8h+j][r]; accumulator reg i of lane l is
-// C[(i&3) + 8*(i>>2) + 4*h][l&31].  M, N multiples of 32, K multiple of 16 (host-checked).
+// C[cd_row32(i, h)][l&31].  M, N multiples of 32, K multiple of 16 (host-checked).
 __global__ void __launch_bounds__(64) mfma_gemm(const short* __restrict__ A, const short* __restrict__ B,
                                                 float* __restrict__ C, int M, int N, int K) {
   const int lane = threadIdx.x;
   const int r = lane & 31, h = lane >> 5;
   const int tm = blockIdx.y * 32, tn = blockIdx.x * 32;
   if (tm + 32 > M || tn + 32 > N) return;  // host checks shapes; never touch memory past them
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int k0 = 0; k0 < K; k0 += 16) {
     bf16x8 a, b;
     for (int j = 0; j < 8; ++j) {
@@ -39,7 +38,7 @@ __global__ void __launch_bounds__(64) mfma_gemm(const short* __restrict__ A, con
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
   }
   for (int i = 0; i < 16; ++i) {
-    const int row = tm + (i & 3) + 8 * (i >> 2) + 4 * h;
+    const int row = tm + cd_row32(i, h);
     C[static_cast<size_t>(row) * N + tn + r] = acc[i];
   }
 }
@@ -74,6 +73,29 @@ __host__ __device__ __forceinline__ void tile_origin128(int block, int nblocks, 
   *n0 = (wg % nbn) * kTileN;
 }
 
+// An operand tile in LDS is [rows][64] bf16: 128 B rows of eight 16 B chunks.  The 16 lanes of
+// one ds_read_b128 cycle (rows r..r+15, same k chunk) would hit 2 of the 16 bank slots of a
+// 256 B bank row (8-way conflict), so the image is swizzled: logical chunk `chunk` of row `row`
+// sits at this physical chunk.  Row parity picks the 128 B half of the bank row and
+// (row >> 1) & 7 the slot in it, so 16 consecutive rows cover all 16 slots (conflict-free, for
+// the 16x16x32 lane groups too; `chunk ^ (row & 7)` measured 2-way, SQ_LDS_BANK_CONFLICT).
+__device__ __forceinline__ int swizzled_chunk(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
+
+// The 8 k values of logical chunk `chunk` of row `row` of tile image S: one ds_read_b128.
+__device__ __forceinline__ bf16x8 frag(const short* S, int row, int chunk) {
+  return *reinterpret_cast<const bf16x8*>(S + row * kTileK + (swizzled_chunk(row, chunk) << 3));
+}
+
+// Piece p of an operand tile: rows 8p .. 8p+7 (1 KiB) of the tile whose first row is r0 and
+// first k is k0, from HBM straight into the image at `base`.  Lane l lands at physical chunk
+// l & 7 of row l >> 3 (the glds destination must stay lane-linear), so the swizzle is applied
+// on its global source address.
+__device__ __forceinline__ void glds_piece(const short* src, int r0, int K, int k0, char* base, int p, int lane) {
+  const int row = p * 8 + (lane >> 3), kc = swizzled_chunk(row, lane & 7) * 8;
+  __builtin_amdgcn_global_load_lds(src + static_cast<size_t>(r0 + row) * K + k0 + kc, (lds_void_ptr)(base + p * 1024),
+                                   16, 0, 0);
+}
+
 __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, const short* __restrict__ Bt,
                                                float* __restrict__ C, int M, int N, int K) {
   // one __shared__ array for everything (a second object can de-pipeline glds waits)
@@ -85,15 +107,8 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
   const int wr = wave >> 1, wc = wave & 1;
   const int r = lane & 31, h = lane >> 5;
 
-  // staging: wave w issues 4 x 1 KiB per operand = rows (4w+i)*8 .. +7; lane l lands at
-  // physical 16 B chunk l&7 of row l>>3.  LDS rows are 128 B, so the 16 lanes of one
-  // ds_read_b128 cycle (rows r..r+15, same k chunk) would hit 2 of the 16 bank slots of
-  // a 256 B bank row (8-way conflict).  The image is swizzled as physical chunk =
-  // logical chunk ^ ((row >> 1) & 7): row parity picks the 128 B half of the bank row
-  // and (row >> 1) & 7 the slot in it, so 16 consecutive rows cover all 16 slots
-  // (conflict-free; `chunk ^ (row & 7)` measured 2-way, SQ_LDS_BANK_CONFLICT).  The
-  // swizzle is applied on the per-lane global source address, since the glds
-  // destination must stay lane-linear.
+  // Wave w issues pieces 4w .. 4w+3 of A and of B.  This is glds_piece written out, here and in
+  // gemm256: with the call in this loop the compiler allocates both kernels' registers differently.
   auto stage = [&](int t, int buf) {
     const int k0 = t * kTileK;
     char* base = smem + buf * 2 * kTileBytes;
@@ -108,8 +123,7 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
 
   f32x16 acc[2][2];
   for (int i = 0; i < 2; ++i)
-    for (int j = 0; j < 2; ++j)
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+    for (int j = 0; j < 2; ++j) acc[i][j] = zero_f32x16();
 
   const int T = K / kTileK;
   stage(0, 0);
@@ -124,14 +138,8 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
     for (int kk = 0; kk < kTileK / 16; ++kk) {
       const int chunk = 2 * kk + h;  // logical 16 B chunk of this lane's 8 k values
       bf16x8 a[2], b[2];
-      for (int i = 0; i < 2; ++i) {
-        const int row = wr * 64 + i * 32 + r;
-        a[i] = *reinterpret_cast<const bf16x8*>(As + row * kTileK + ((chunk ^ ((row >> 1) & 7)) << 3));
-      }
-      for (int j = 0; j < 2; ++j) {
-        const int row = wc * 64 + j * 32 + r;
-        b[j] = *reinterpret_cast<const bf16x8*>(Bs + row * kTileK + ((chunk ^ ((row >> 1) & 7)) << 3));
-      }
+      for (int i = 0; i < 2; ++i) a[i] = frag(As, wr * 64 + i * 32 + r, chunk);
+      for (int j = 0; j < 2; ++j) b[j] = frag(Bs, wc * 64 + j * 32 + r, chunk);
       for (int i = 0; i < 2; ++i)
         for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
     }
@@ -141,7 +149,7 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
   for (int i = 0; i < 2; ++i)
     for (int j = 0; j < 2; ++j)
       for (int e = 0; e < 16; ++e) {
-        const int row = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int row = m0 + wr * 64 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;  // cd_row32, in this order of sums
         C[static_cast<size_t>(row) * N + n0 + wc * 64 + j * 32 + r] = acc[i][j][e];
       }
 }
@@ -164,12 +172,13 @@ __global__ void __launch_bounds__(256) gemm_lds(const short* __restrict__ A, con
 // barrier 4t+8, which precedes the first read of tile t+2.  The DMA therefore stays in
 // flight across three barriers (__syncthreads would drain it at each: vmcnt(0)).
 // Write-after-read is covered by every reading section ending in lgkmcnt(0) before its
-// barrier.  Row swizzle as in gemm_lds (chunk ^ ((row >> 1) & 7)): conflict-free for the
-// 16x16x32 lane groups too.  Tiles are rastered in groups of 4 tile rows, so one XCD's
-// consecutive workgroups share 4 A panels and a run of B panels in their L2.
-constexpr int kBT = 256, kBK = 64;
-constexpr int kBOp = kBT * kBK * 2;  // one operand tile, 32 KiB
-constexpr int kBStage = 2 * kBOp;    // A + B of one K-tile, 64 KiB
+// barrier.  The LDS image is gemm_lds's (swizzled_chunk).  Tiles are rastered in groups of 4
+// tile rows, so one XCD's consecutive workgroups share 4 A panels and a run of B panels in
+// their L2.
+constexpr int kBT = 256, kBK = kTileK;  // the same 128 B LDS rows, so frag and glds_piece serve here too
+constexpr int kBOp = kBT * kBK * 2;     // one operand tile, 32 KiB
+constexpr int kBStage = 2 * kBOp;       // A + B of one K-tile, 64 KiB
+constexpr int kGroupM256 = 4;           // tile rows per raster group
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // Output tile of workgroup `block` of `nblocks`: XCD-aware bijective remap, then tiles rastered
@@ -184,9 +193,6 @@ __host__ __device__ __forceinline__ void tile_origin256(int block, int nblocks, 
   *n0 = ((wg % per_group) / gm) * kBT;
 }
 
-// Tile rows per raster group of kernel id `kind` (2-11, see pick_gemm): gemm256s's kGroupM.
-constexpr int gemm_group(int kind) { return kind == 9 ? 2 : kind == 10 ? 8 : 4; }
-
 __device__ __forceinline__ void section_end() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this section's LDS reads are done
   __builtin_amdgcn_s_barrier();
@@ -194,18 +200,43 @@ __device__ __forceinline__ void section_end() {
   __builtin_amdgcn_sched_barrier(0);  // nothing crosses a section boundary
 }
 
+// The parts gemm256 and gemm256s share.  Their L sections (the frag loops) stay written out in
+// both kernels, and so does gemm256's M0: as calls they change the kernels' register allocation.
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[2][4][4]) {
+#pragma unroll
+  for (int h = 0; h < 2; ++h)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+// An M section: 32 MFMA into one half's 4x4 tiles, under raised wave priority when kPrio.
+template <bool kPrio>
+__device__ __forceinline__ void mfma_section(f32x4 (&acc)[4][4], const bf16x8 (&a)[4][2], const bf16x8 (&b)[4][2]) {
+  if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+  for (int s = 0; s < 2; ++s)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s], b[j][s], acc[i][j], 0, 0, 0);
+  if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+}
+
 __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, const short* __restrict__ Bt,
                                               float* __restrict__ C, int M, int N, int K) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kBStage];  // the only LDS object
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   int m0, n0;
-  tile_origin256(blockIdx.x, gridDim.x, M, N, gemm_group(2), &m0, &n0);
+  tile_origin256(blockIdx.x, gridDim.x, M, N, kGroupM256, &m0, &n0);
   if (m0 + kBT > M || n0 + kBT > N) return;  // host checks shapes (block-uniform exit)
   const int wr = wave >> 2, wc = wave & 3;
   const bool g1 = wr == 1;
   const int r16 = lane & 15, q = lane >> 4;
 
-  auto stage = [&](int t) {  // 8 x 1 KiB pieces per wave: rows (4w+i)*8 .. +7 of A and of B
+  auto stage = [&](int t) {  // pieces 4w .. 4w+3 of A and of B per wave, written out as in gemm_lds
     const int k0 = t * kBK;
     char* base = smem + (t & 1) * kBStage;
 #pragma unroll
@@ -217,17 +248,9 @@ __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, cons
                                        (lds_void_ptr)(base + kBOp + (wave * 4 + i) * 1024), 16, 0, 0);
     }
   };
-  auto frag = [&](const short* S, int row, int chunk) {
-    return *reinterpret_cast<const bf16x8*>(S + row * kBK + ((chunk ^ ((row >> 1) & 7)) << 3));
-  };
 
   f32x4 acc[2][4][4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   bf16x8 a[4][2], b[4][2];
 
   const int T = K / kBK;
@@ -255,7 +278,7 @@ __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, cons
 #pragma unroll
       for (int i = 0; i < 4; ++i) a[i][s] = frag(As, wr * 128 + i * 16 + r16, 4 * s + q);
     section_end();
-    // M0
+    // M0: mfma_section<true>(acc[0], a, b), written out
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int s = 0; s < 2; ++s)
@@ -275,15 +298,7 @@ __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, cons
     section_end();
     // M1
     if (g1 && t + 2 < T) stage(t + 2);
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s = 0; s < 2; ++s)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[1][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s], b[j][s], acc[1][i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
+    mfma_section<true>(acc[1], a, b);
     if (!g1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile t+1 (issued in interval 4t)
     section_end();
   }
@@ -321,7 +336,7 @@ __global__ void __launch_bounds__(512) gemm256(const short* __restrict__ A, cons
 // kScalarWave: the wave index goes through readfirstlane, so everything derived from it
 // (LDS piece addresses -> M0, group branches) is scalar instead of per-lane.
 // kGroupM: tile rows per raster group; kPrio: raise wave priority around MFMA sections.
-template <int kBEarly, bool kG1Early = false, bool kScalarWave = true, int kGroupM = 4, bool kPrio = true>
+template <int kBEarly, bool kG1Early = false, bool kScalarWave = true, int kGroupM = kGroupM256, bool kPrio = true>
 __global__ void __launch_bounds__(512) gemm256s(const short* __restrict__ A, const short* __restrict__ Bt,
                                                float* __restrict__ C, int M, int N, int K) {
   __shared__ __attribute__((aligned(16))) char smem[2 * kBStage];  // the only LDS object
@@ -334,53 +349,31 @@ __global__ void __launch_bounds__(512) gemm256s(const short* __restrict__ A, con
   const bool g1 = wr == 1;
   const int r16 = lane & 15, q = lane >> 4;
 
-  // piece p = rows 8p .. 8p+7 of one operand (1 KiB, 128 B rows, swizzled source)
-  auto piece = [&](const short* src, int r0, char* base, int p, int k0) {
-    const int row = p * 8 + (lane >> 3), kc = ((lane & 7) ^ ((row >> 1) & 7)) * 8;
-    __builtin_amdgcn_global_load_lds(src + static_cast<size_t>(r0 + row) * K + k0 + kc, (lds_void_ptr)(base + p * 1024),
-                                     16, 0, 0);
-  };
   // A-h0 pieces are 0-7 and 16-23, A-h1 pieces 8-15 and 24-31; wave w owns list entries 2w, 2w+1
   auto a_piece = [](int k, int half) { return (k < 8 ? k : k + 8) + 8 * half; };
   auto stage_b_ah0 = [&](int t) {  // kBEarly B + 2 A-h0 pieces
     char* base = smem + (t & 1) * kBStage;
 #pragma unroll
-    for (int i = 0; i < kBEarly; ++i) piece(Bt, n0, base + kBOp, wave * 4 + i, t * kBK);
+    for (int i = 0; i < kBEarly; ++i) glds_piece(Bt, n0, K, t * kBK, base + kBOp, wave * 4 + i, lane);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) piece(A, m0, base, a_piece(wave * 2 + i, 0), t * kBK);
+    for (int i = 0; i < 2; ++i) glds_piece(A, m0, K, t * kBK, base, a_piece(wave * 2 + i, 0), lane);
   };
   auto stage_ah1 = [&](int t) {  // 4 - kBEarly B + 2 A-h1 pieces
     char* base = smem + (t & 1) * kBStage;
 #pragma unroll
-    for (int i = kBEarly; i < 4; ++i) piece(Bt, n0, base + kBOp, wave * 4 + i, t * kBK);
+    for (int i = kBEarly; i < 4; ++i) glds_piece(Bt, n0, K, t * kBK, base + kBOp, wave * 4 + i, lane);
 #pragma unroll
-    for (int i = 0; i < 2; ++i) piece(A, m0, base, a_piece(wave * 2 + i, 1), t * kBK);
-  };
-  auto frag = [&](const short* S, int row, int chunk) {
-    return *reinterpret_cast<const bf16x8*>(S + row * kBK + ((chunk ^ ((row >> 1) & 7)) << 3));
+    for (int i = 0; i < 2; ++i) glds_piece(A, m0, K, t * kBK, base, a_piece(wave * 2 + i, 1), lane);
   };
   auto retire = [&](int t) {  // tile t+1 landed; tile t+2's 2 + kBEarly pieces may fly on
     if (t + 2 >= K / kBK)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if constexpr (kBEarly == 4)
-      asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-    else if constexpr (kBEarly == 3)
-      asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-    else if constexpr (kBEarly == 2)
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else if constexpr (kBEarly == 1)
-      asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
     else
-      asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 + kBEarly) : "memory");
   };
 
   f32x4 acc[2][4][4];
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   bf16x8 a[4][2], b[4][2];
 
   const int T = K / kBK;
@@ -412,15 +405,7 @@ __global__ void __launch_bounds__(512) gemm256s(const short* __restrict__ A, con
     section_end();
     // M0
     if (kG1Early && g1 && t + 2 < T) stage_b_ah0(t + 2);
-    if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[0][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s2], b[j][s2], acc[0][i][j], 0, 0, 0);
-    if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+    mfma_section<kPrio>(acc[0], a, b);
     section_end();
     // L1
     if ((!kG1Early || !g1) && t + 2 < T) stage_b_ah0(t + 2);
@@ -432,15 +417,7 @@ __global__ void __launch_bounds__(512) gemm256s(const short* __restrict__ A, con
     section_end();
     // M1
     if (kG1Early && g1 && t + 2 < T) stage_ah1(t + 2);
-    if constexpr (kPrio) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          acc[1][i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[i][s2], b[j][s2], acc[1][i][j], 0, 0, 0);
-    if constexpr (kPrio) __builtin_amdgcn_s_setprio(0);
+    mfma_section<kPrio>(acc[1], a, b);
     if (!g1) retire(t);
     section_end();
   }
@@ -561,44 +538,46 @@ __global__ void __launch_bounds__(256) gemm_abft(const short* __restrict__ X, co
   if (tid == 0 && (red[0][0] != red[1][0] || red[2][0] != 0)) atomicAdd(errors + mode, 1ull);
 }
 
-// GEMM kernel choice: 1 = gemm_lds (128x128 tiles), 2 = gemm256 (256x256 tiles, wave-group
-// ping-pong), 3 = gemm256s (same, region-wise DMA from the LDS-read sections); 0 = gemm256s
-// when the shape divides into 256x256 tiles and gives at least 256 of them (one per CU),
-// else gemm_lds.  Returns 0 for a shape the kernel cannot take.
+// What a GEMM kernel id means: the edge of its square output tiles (one workgroup each), the tile
+// rows per raster group (0: gemm_lds rasters row-major), its block size and the kernel.
+using gemm_fn = void (*)(const short*, const short*, float*, int, int, int);
+struct GemmVariant {
+  int tile, group, threads;
+  gemm_fn kernel;
+};
+template <int kBEarly, bool kG1Early = false, bool kScalarWave = true, int kGroupM = kGroupM256, bool kPrio = true>
+constexpr GemmVariant staged = {kBT, kGroupM, 512, gemm256s<kBEarly, kG1Early, kScalarWave, kGroupM, kPrio>};
+
+constexpr GemmVariant kGemmVariants[] = {
+    {},                                  // 0 is no kernel: pick_gemm's own choice
+    {kTileM, 0, 256, gemm_lds},          // 1 128x128 tiles
+    {kBT, kGroupM256, 512, gemm256},     // 2 256x256 tiles, wave-group ping-pong, whole-tile DMA
+    staged<4>,                           // 3 region-wise DMA from the LDS-read sections
+    staged<2>,                           // 4 ... 2 of a wave's 4 B pieces early
+    staged<0>,                           // 5 ... none
+    staged<3>,                           // 6 ... 3
+    staged<4, true>,                     // 7 group 1 refills from its MFMA sections
+    staged<4, false, false>,             // 8 per-lane wave index
+    staged<4, false, true, 2>,           // 9 raster groups of 2 tile rows
+    staged<4, false, true, 8>,           // 10 ... of 8
+    staged<4, false, true, 4, false>,    // 11 no wave priority around MFMA sections
+};
+constexpr int kGemmVariantCount = sizeof(kGemmVariants) / sizeof(kGemmVariants[0]);
+
+// GEMM kernel choice: `kernel` itself if it is an id of kGemmVariants whose tiles divide the
+// shape; for 0, gemm256s (3) when the shape divides into 256x256 tiles and gives at least 256
+// of them (one per CU), else gemm_lds (1).  Returns 0 for a shape the kernel cannot take.
 int pick_gemm(int M, int N, int K, int kernel) {
-  if (M <= 0 || N <= 0 || K <= 0 || K % kTileK) return 0;
-  const bool fits256 = M % kBT == 0 && N % kBT == 0, fits128 = M % kTileM == 0 && N % kTileN == 0;
-  if (kernel >= 2 && kernel <= 11) return fits256 ? kernel : 0;
-  if (kernel == 1) return fits128 ? 1 : 0;
-  if (kernel != 0) return 0;
-  if (fits256 && (M / kBT) * (N / kBT) >= 256) return 3;
-  return fits128 ? 1 : 0;
+  if (M <= 0 || N <= 0 || K <= 0 || K % kTileK || kernel < 0 || kernel >= kGemmVariantCount) return 0;
+  const auto fits = [&](int id) { return M % kGemmVariants[id].tile == 0 && N % kGemmVariants[id].tile == 0; };
+  if (kernel != 0) return fits(kernel) ? kernel : 0;
+  if (fits(3) && (M / kBT) * (N / kBT) >= 256) return 3;
+  return fits(1) ? 1 : 0;
 }
 
 void launch_gemm(int kind, const short* a, const short* b, float* c, int M, int N, int K) {
-  const dim3 g256((M / kBT) * (N / kBT)), b256(512);
-  if (kind == 3)
-    hipLaunchKernelGGL(gemm256s<4>, g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 4)
-    hipLaunchKernelGGL(gemm256s<2>, g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 5)
-    hipLaunchKernelGGL(gemm256s<0>, g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 6)
-    hipLaunchKernelGGL(gemm256s<3>, g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 7)
-    hipLaunchKernelGGL((gemm256s<4, true>), g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 8)
-    hipLaunchKernelGGL((gemm256s<4, false, false>), g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 9)
-    hipLaunchKernelGGL((gemm256s<4, false, true, gemm_group(9)>), g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 10)
-    hipLaunchKernelGGL((gemm256s<4, false, true, gemm_group(10)>), g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 11)
-    hipLaunchKernelGGL((gemm256s<4, false, true, 4, false>), g256, b256, 0, 0, a, b, c, M, N, K);
-  else if (kind == 2)
-    hipLaunchKernelGGL(gemm256, dim3((M / kBT) * (N / kBT)), dim3(512), 0, 0, a, b, c, M, N, K);
-  else
-    hipLaunchKernelGGL(gemm_lds, dim3((M / kTileM) * (N / kTileN)), dim3(256), 0, 0, a, b, c, M, N, K);
+  const GemmVariant& v = kGemmVariants[kind];
+  hipLaunchKernelGGL(v.kernel, dim3((M / v.tile) * (N / v.tile)), dim3(v.threads), 0, 0, a, b, c, M, N, K);
 }
 
 // The numerics tests' path: operands from host memory, `launch(a, b, c)` on them, C back to the host.
@@ -623,21 +602,47 @@ int gemm_on_host_data(int device, const unsigned short* a_host, size_t a_bytes, 
   return st.report("", err, err_len);
 }
 
-// The checksum sequence: the column sums of A and of Bt, then the row and the column verdicts
-// on C.  asum and bsum hold K sums each; counts[0] += wrong rows, counts[1] += wrong columns
-// (the caller zeroes counts).  Shape-generic: any positive M, N, K.
-void abft_checksums(Status& st, const short* a, const short* bt, const float* c, DeviceBuffer<long long>& asum,
-                    DeviceBuffer<long long>& bsum, unsigned long long* counts, int M, int N, int K) {
-  CANARY_HIP(st, asum.zero());
-  CANARY_HIP(st, bsum.zero());
-  if (!st.ok()) return;
-  const int kb = (K + 255) / 256;
-  hipLaunchKernelGGL(gemm_colsum, dim3(kb, (M + kSlab - 1) / kSlab), dim3(256), 0, 0, a, M, K, asum.get());
-  hipLaunchKernelGGL(gemm_colsum, dim3(kb, (N + kSlab - 1) / kSlab), dim3(256), 0, 0, bt, N, K, bsum.get());
-  hipLaunchKernelGGL(gemm_abft, dim3(M), dim3(256), 0, 0, a, c, bsum.get(), M, N, K, 0, counts);
-  hipLaunchKernelGGL(gemm_abft, dim3(N), dim3(256), 0, 0, bt, c, asum.get(), M, N, K, 1, counts);
-  st.check(hipGetLastError());
-}
+// Owns the device side of one ABFT-verified product: A [MxK], Bt [NxK], C [MxN], the K column
+// sums of A and of Bt, and the two counters (wrong rows, wrong columns).
+class AbftProduct {
+ public:
+  DeviceBuffer<short> a, b;
+  DeviceBuffer<float> c;
+
+  // selects the device; the counters start at zero
+  void alloc(Status& st, int device, int M, int N, int K) {
+    CANARY_HIP(st, hipSetDevice(device));
+    CANARY_HIP(st, a.alloc(static_cast<size_t>(M) * K * 2));
+    CANARY_HIP(st, b.alloc(static_cast<size_t>(N) * K * 2));
+    CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
+    CANARY_HIP(st, asum_.alloc(static_cast<size_t>(K) * 8));
+    CANARY_HIP(st, bsum_.alloc(static_cast<size_t>(K) * 8));
+    CANARY_HIP(st, counts_.alloc(2 * sizeof(unsigned long long)));
+    CANARY_HIP(st, counts_.zero());
+  }
+  // The checksum sequence: the column sums of A and of Bt, then the row and the column verdicts
+  // on C, added to the counters.  Shape-generic: any positive M, N, K.
+  void verify(Status& st, int M, int N, int K) {
+    CANARY_HIP(st, asum_.zero());
+    CANARY_HIP(st, bsum_.zero());
+    if (!st.ok()) return;
+    const int kb = (K + 255) / 256;
+    hipLaunchKernelGGL(gemm_colsum, dim3(kb, (M + kSlab - 1) / kSlab), dim3(256), 0, 0, a.get(), M, K, asum_.get());
+    hipLaunchKernelGGL(gemm_colsum, dim3(kb, (N + kSlab - 1) / kSlab), dim3(256), 0, 0, b.get(), N, K, bsum_.get());
+    hipLaunchKernelGGL(gemm_abft, dim3(M), dim3(256), 0, 0, a.get(), c.get(), bsum_.get(), M, N, K, 0, counts_.get());
+    hipLaunchKernelGGL(gemm_abft, dim3(N), dim3(256), 0, 0, b.get(), c.get(), asum_.get(), M, N, K, 1, counts_.get());
+    st.check(hipGetLastError());
+  }
+  // waits for the device; counts = {wrong rows, wrong columns}
+  void finish(Status& st, unsigned long long (&counts)[2]) {
+    CANARY_HIP(st, hipDeviceSynchronize());
+    CANARY_HIP(st, counts_.download(counts));
+  }
+
+ private:
+  DeviceBuffer<long long> asum_, bsum_;
+  DeviceBuffer<unsigned long long> counts_;
+};
 
 }  // namespace
 
@@ -649,12 +654,13 @@ extern "C" {
 int amdgpu_canary_gemm_tile_map(int kernel, int M, int N, int* m0_out, int* n0_out, int len) {
   const int kind = pick_gemm(M, N, kTileK, kernel);
   if (kind == 0) return 0;
-  const int grid = kind == 1 ? (M / kTileM) * (N / kTileN) : (M / kBT) * (N / kBT);
+  const GemmVariant& v = kGemmVariants[kind];
+  const int grid = (M / v.tile) * (N / v.tile);
   for (int b = 0; b < grid && b < len; ++b) {
-    if (kind == 1)
+    if (v.tile == kTileM)
       tile_origin128(b, grid, M, N, &m0_out[b], &n0_out[b]);
     else
-      tile_origin256(b, grid, M, N, gemm_group(kind), &m0_out[b], &n0_out[b]);
+      tile_origin256(b, grid, M, N, v.group, &m0_out[b], &n0_out[b]);
   }
   return grid;
 }
@@ -671,25 +677,14 @@ int amdgpu_canary_abft(int device, const unsigned short* a_host, const unsigned 
     return -1;
   }
   Status st;
-  DeviceBuffer<short> a, b;
-  DeviceBuffer<float> c;
-  DeviceBuffer<long long> asum, bsum;
-  DeviceBuffer<unsigned long long> d_err;
+  AbftProduct p;
   unsigned long long counts[2] = {0, 0};
-  CANARY_HIP(st, hipSetDevice(device));
-  CANARY_HIP(st, a.alloc(static_cast<size_t>(M) * K * 2));
-  CANARY_HIP(st, b.alloc(static_cast<size_t>(N) * K * 2));
-  CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
-  CANARY_HIP(st, asum.alloc(static_cast<size_t>(K) * 8));
-  CANARY_HIP(st, bsum.alloc(static_cast<size_t>(K) * 8));
-  CANARY_HIP(st, d_err.alloc(sizeof(counts)));
-  CANARY_HIP(st, d_err.zero());
-  CANARY_HIP(st, a.upload(a_host));
-  CANARY_HIP(st, b.upload(bt_host));
-  CANARY_HIP(st, c.upload(c_host));
-  abft_checksums(st, a.get(), b.get(), c.get(), asum, bsum, d_err.get(), M, N, K);
-  CANARY_HIP(st, hipDeviceSynchronize());
-  CANARY_HIP(st, d_err.download(counts));
+  p.alloc(st, device, M, N, K);
+  CANARY_HIP(st, p.a.upload(a_host));
+  CANARY_HIP(st, p.b.upload(bt_host));
+  CANARY_HIP(st, p.c.upload(c_host));
+  p.verify(st, M, N, K);
+  p.finish(st, counts);
   *row_errors = counts[0];
   *col_errors = counts[1];
   return st.report("", err, err_len);
@@ -747,51 +742,37 @@ int amdgpu_canary_gemm_rate(int device, int M, int N, int K, int iters, int flag
     return -1;
   }
   Status st;
-  DeviceBuffer<short> a, b;
-  DeviceBuffer<float> c;
-  DeviceBuffer<long long> asum, bsum;
-  DeviceBuffer<unsigned long long> d_err;
+  AbftProduct p;
   Events<2> ev;
   float ms[1] = {0};
-  CANARY_HIP(st, hipSetDevice(device));
-  CANARY_HIP(st, a.alloc(static_cast<size_t>(M) * K * 2));
-  CANARY_HIP(st, b.alloc(static_cast<size_t>(N) * K * 2));
-  CANARY_HIP(st, c.alloc(static_cast<size_t>(M) * N * 4));
-  CANARY_HIP(st, asum.alloc(static_cast<size_t>(K) * 8));
-  CANARY_HIP(st, bsum.alloc(static_cast<size_t>(K) * 8));
   unsigned long long counts[2] = {0, 0};
-  CANARY_HIP(st, d_err.alloc(sizeof(counts)));
-  CANARY_HIP(st, d_err.zero());
+  p.alloc(st, device, M, N, K);
   CANARY_HIP(st, ev.create());
+  const auto launch = [&] { launch_gemm(kind, p.a.get(), p.b.get(), p.c.get(), M, N, K); };
   if (st.ok()) {
-    if (random_data) {
-      hipLaunchKernelGGL(gemm_fill_random, dim3(2048), dim3(256), 0, 0, a.get(), M, K, 1u);
-      hipLaunchKernelGGL(gemm_fill_random, dim3(2048), dim3(256), 0, 0, b.get(), N, K, 2u);
-    } else {
-      hipLaunchKernelGGL(gemm_fill, dim3(2048), dim3(256), 0, 0, a.get(), M, K, 1u);
-      hipLaunchKernelGGL(gemm_fill, dim3(2048), dim3(256), 0, 0, b.get(), N, K, 2u);
-    }
-    launch_gemm(kind, a.get(), b.get(), c.get(), M, N, K);  // warm-up
+    const auto fill = random_data ? gemm_fill_random : gemm_fill;
+    hipLaunchKernelGGL(fill, dim3(2048), dim3(256), 0, 0, p.a.get(), M, K, 1u);
+    hipLaunchKernelGGL(fill, dim3(2048), dim3(256), 0, 0, p.b.get(), N, K, 2u);
+    launch();  // warm-up
     st.check(hipGetLastError());
   }
   time_stages(st, ev, ms, [&](int) {
-    for (int i = 0; i < iters; ++i) launch_gemm(kind, a.get(), b.get(), c.get(), M, N, K);
+    for (int i = 0; i < iters; ++i) launch();
     return hipSuccess;
   });
   if (!random_data) {
-    CANARY_HIP(st, c.fill(0xFF));  // the poison: what is verified below was written after it
+    CANARY_HIP(st, p.c.fill(0xFF));  // the poison: what is verified below was written after it
     if (st.ok() && !skip_verified_launch) {
-      launch_gemm(kind, a.get(), b.get(), c.get(), M, N, K);
+      launch();
       st.check(hipGetLastError());
     }
   }
   if (inject) {
     const float junk = 12345.0f;
-    CANARY_HIP(st, hipMemcpy(c.get() + static_cast<size_t>(M / 2) * N + N / 3, &junk, 4, hipMemcpyHostToDevice));
+    CANARY_HIP(st, hipMemcpy(p.c.get() + static_cast<size_t>(M / 2) * N + N / 3, &junk, 4, hipMemcpyHostToDevice));
   }
-  if (!random_data) abft_checksums(st, a.get(), b.get(), c.get(), asum, bsum, d_err.get(), M, N, K);
-  CANARY_HIP(st, hipDeviceSynchronize());
-  CANARY_HIP(st, d_err.download(counts));
+  if (!random_data) p.verify(st, M, N, K);
+  p.finish(st, counts);
   *errors = counts[0] + counts[1];
   if (st.ok() && ms[0] > 0) *tflops = 2.0 * M * N * K * iters / (ms[0] * 1e-3) / 1e12;
   return st.report("", err, err_len);

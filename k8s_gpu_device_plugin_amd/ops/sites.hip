@@ -91,8 +91,7 @@ void valu_expected(uint32_t* digest) {  // the 64 lanes of one wave, shuffle emu
 // ---- the three checks: wrong results this lane sees --------------------------------
 __device__ __forceinline__ uint32_t check_mfma(uint32_t key, int lane, int ksteps, bool inject) {
   const int r = lane & 31, h = lane >> 5;
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int s = 0; s < ksteps; ++s) {
     bf16x8 a, b;
     for (int j = 0; j < 8; ++j) {
@@ -104,7 +103,7 @@ __device__ __forceinline__ uint32_t check_mfma(uint32_t key, int lane, int kstep
   }
   uint32_t bad = 0;
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;  // C/D map of 32x32x16
+    const int row = cd_row32(reg, h);
     int ref = 0;
     for (int k = 0; k < ksteps * 16; ++k) ref += a_val(key, row, k) * b_val(key, k, r);
     bad += acc[reg] != static_cast<float>(ref);
@@ -115,8 +114,7 @@ __device__ __forceinline__ uint32_t check_mfma(uint32_t key, int lane, int kstep
 __device__ __forceinline__ uint32_t check_lowp(uint32_t key, int lane, int ksteps, bool inject) {
   const int r = lane & 31, h = lane >> 5;
   const uint32_t blk = key + (static_cast<uint32_t>(kFp8 + 1) << 20);  // as lowp_exact<kFp8>
-  f32x16 acc;
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  f32x16 acc = zero_f32x16();
   for (int s = 0; s < ksteps; ++s) {
     i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
@@ -133,7 +131,7 @@ __device__ __forceinline__ uint32_t check_lowp(uint32_t key, int lane, int kstep
   }
   uint32_t bad = 0;
   for (int reg = 0; reg < 16; ++reg) {
-    const int row = (reg & 3) + 8 * (reg >> 2) + 4 * h;
+    const int row = cd_row32(reg, h);
     int ref = 0;
     for (int kb = 0; kb < 2 * ksteps; ++kb) {
       int part = 0;

@@ -5,13 +5,11 @@ start-up canary's log line."""
 import ctypes
 import json
 import logging
-import re
-import subprocess
 import time
 
 import pytest
 
-from k8s_gpu_device_plugin_amd import _build
+from kernel_usage import kernel_resource_usage
 from k8s_gpu_device_plugin_amd.ops import canary
 from k8s_gpu_device_plugin_amd.plugin.kubelet_stub import KubeletStub
 from k8s_gpu_device_plugin_amd.plugin.manager import PluginManager
@@ -32,22 +30,7 @@ def test_reg_march_builds_without_scratch_at_occupancy_one(tmp_path):
     """The march is a register-file test only while no marched value lives in scratch memory
     and a wave is allocated the SIMD's whole file: both are read from the compiler's own
     resource-usage remarks, so a compiler upgrade cannot change them silently."""
-    src = [s for s in _build.CANARY_SOURCES if s.endswith("cumem.hip")]
-    assert len(src) == 1
-    p = subprocess.run([_build.hipcc_path(), "--offload-arch=" + _build.OFFLOAD_ARCH, "-O3", "-std=c++17", "-fPIC",
-                        "-c", "-Rpass-analysis=kernel-resource-usage", src[0], "-o", str(tmp_path / "cumem.o")],
-                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-    assert p.returncode == 0, p.stdout[-2000:]
-    usage, name = {}, None
-    for line in p.stdout.splitlines():
-        m = re.search(r"remark:\s+Function Name: (\S+)", line)
-        if m:
-            name = m.group(1)
-            usage[name] = {}
-            continue
-        m = re.search(r"remark:\s+([A-Za-z][^:\[]*?)(?: \[[^\]]*\])?: (\S+) \[-Rpass", line)
-        if m and name:
-            usage[name][m.group(1)] = m.group(2)
+    usage = kernel_resource_usage("cumem.hip", tmp_path)
     march = [u for n, u in usage.items() if "reg_march" in n]
     assert len(march) == 1, sorted(usage)
     u = march[0]

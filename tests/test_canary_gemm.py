@@ -1,5 +1,5 @@
 """The matrix path of the canary (``ops/gemm.hip``) as far as it can be checked without a GPU:
-the tile maps of every GEMM kernel id (the kernels' own index arithmetic, run on the host by
+the build contract of the LDS-staged kernels, the tile maps of every GEMM kernel id (the kernels' own index arithmetic, run on the host by
 ``amdgpu_canary_gemm_tile_map``), the shape validators of ``gemm``, ``gemm_rate`` and ``abft``
 (refused by their own message, so before any HIP call), and the numpy model of the ABFT verdict
 that ``tests/test_gpu_gemm.py`` uses as the oracle of the device verifier."""
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import abft_model as model
+from kernel_usage import kernel_resource_usage
 from k8s_gpu_device_plugin_amd.ops import canary
 
 IDS = sorted(v for v in canary.GEMM_KERNELS.values() if v != 0)
@@ -29,6 +30,28 @@ def _xcd_remap(block, nblocks):
     xcd, q, r = block % 8, nblocks // 8, nblocks % 8
     start = xcd * (q + 1) if xcd < r else r * (q + 1) + (xcd - r) * q
     return start + block // 8
+
+
+# ---- build contract ------------------------------------------------------------------------
+def test_gemm_kernels_build_without_scratch_at_occupancy_two(tmp_path):
+    """What the LDS-staged kernels' schedules assume, read from the compiler's own resource-usage
+    remarks: nothing spills, the one LDS array is 2 buffers x 2 operands x 16 KiB (gemm_lds) or
+    2 x 64 KiB (the 256x256 kernels: one block per CU), and a 512-thread block's 8 waves fit the
+    CU as 2 per SIMD of a 512-entry register file."""
+    usage = kernel_resource_usage("gemm.hip", tmp_path)
+    lds128 = [n for n in usage if "gemm_lds" in n]
+    staged = [n for n in usage if "gemm256s" in n]
+    whole = [n for n in usage if "gemm256" in n and n not in staged]
+    assert (len(lds128), len(whole), len(staged)) == (1, 1, 9), sorted(usage)
+    for name in lds128 + whole + staged:
+        u = usage[name]
+        print("%s: %s" % (name, u))
+        assert int(u["ScratchSize"]) == 0
+        assert int(u["SGPRs Spill"]) == 0 and int(u["VGPRs Spill"]) == 0
+        assert int(u["LDS Size"]) == (65536 if name in lds128 else 131072)
+        if name not in lds128:
+            assert int(u["VGPRs"]) + int(u["AGPRs"]) <= 256
+        assert int(u["Occupancy"]) == 2
 
 
 # ---- tile maps ---------------------------------------------------------------------------
