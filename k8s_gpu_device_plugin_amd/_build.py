@@ -6,6 +6,8 @@ the repo snapshot to the GPU box):
   native HTTP/2 gRPC server) + pybind11 bindings, linked against ``libamd_smi``.
 * ``k8s_gpu_device_plugin_amd/ops/libamdgpu_canary.so``  HIP/CDNA4 health canary,
   ``hipcc --offload-arch=gfx950``.
+* ``k8s_gpu_device_plugin_amd/ops/hostlink/libamdgpu_hostlink.so``  the canary's host-link
+  check (PCIe reads, writes, copies, system atomics), same ``hipcc`` line.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -66,6 +68,11 @@ CANARY_SOURCES = [os.path.join(PKG_DIR, "ops", f) for f in ("canary.hip", "hbm.h
                                                                "sites.hip", "fabric.hip", "cumem.hip")]
 CANARY_HEADERS = [os.path.join(PKG_DIR, "ops", f) for f in ("canary_common.h", "canary_host.h")]
 CANARY_LIB = os.path.join(PKG_DIR, "ops", "libamdgpu_canary.so")
+# the host-link check: a library of its own next to the canary's, sharing its header-only helpers
+HOSTLINK_DIR = os.path.join(PKG_DIR, "ops", "hostlink")
+HOSTLINK_SOURCES = [os.path.join(HOSTLINK_DIR, "hostlink.hip")]
+HOSTLINK_HEADERS = [os.path.join(HOSTLINK_DIR, f) for f in ("hostlink.h", "hostlink_host.h")] + CANARY_HEADERS
+HOSTLINK_LIB = os.path.join(HOSTLINK_DIR, "libamdgpu_hostlink.so")
 
 
 def native_ext_path() -> str:
@@ -325,10 +332,26 @@ def build_canary(force: bool = False, verbose: bool = True) -> str:
     return CANARY_LIB
 
 
+def build_hostlink(force: bool = False, verbose: bool = True) -> str:
+    """hipcc the host-link check (``ops/hostlink/``) for gfx950 only, as ``build_canary`` does."""
+    hipcc = hipcc_path()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
+    if force or _stale(HOSTLINK_LIB, HOSTLINK_SOURCES + HOSTLINK_HEADERS):
+        tmp = HOSTLINK_LIB + ".tmp"
+        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
+              "-Wall", "-o", tmp] + HOSTLINK_SOURCES, "hipcc hostlink")
+        os.replace(tmp, HOSTLINK_LIB)
+        if verbose:
+            print("built", os.path.relpath(HOSTLINK_LIB, ROOT))
+    return HOSTLINK_LIB
+
+
 def build_all(force: bool = False) -> None:
     build_native(force=force)
     build_bench(force=force)
     build_canary(force=force)
+    build_hostlink(force=force)
 
 
 def main(argv=None) -> int:
@@ -365,6 +388,7 @@ def main(argv=None) -> int:
     build_bench(force=args.force)
     if not args.no_canary:
         build_canary(force=args.force)
+        build_hostlink(force=args.force)
     return 0
 
 

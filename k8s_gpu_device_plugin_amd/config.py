@@ -89,6 +89,12 @@ class HealthConfig:
     # canary like a wrong result does (thermal or power throttling, a degraded HBM stack)
     canaryMinHbmGbps: float = 0.0
     canaryMinTflops: float = 0.0
+    # the canary's host-link check (PCIe reads, writes, copies, system atomics) in every run,
+    # over this many bytes of pinned host memory (a positive multiple of 16), and a floor
+    # (0 = off) on the smallest of its four rates
+    canaryHostLink: bool = False
+    canaryHostLinkBytes: int = 64 << 20
+    canaryMinHostGbps: float = 0.0
     rejectUnhealthyAllocate: bool = True
     # retired + pending HBM pages at which a GPU goes Unhealthy: 0 = the GPU's own RAS
     # threshold when readable (root), -1 = never, N > 0 = N
@@ -389,6 +395,11 @@ def validate(cfg: Config) -> Config:
         raise ConfigError("health.pcieDebounceSamples must be >= 1")
     if cfg.health.discoveryTimeoutS <= 0:
         raise ConfigError("health.discoveryTimeoutS must be > 0")
+    hl_bytes = cfg.health.canaryHostLinkBytes
+    if isinstance(hl_bytes, bool) or not isinstance(hl_bytes, int) or hl_bytes <= 0 or hl_bytes % 16 != 0:
+        raise ConfigError("health.canaryHostLinkBytes must be a positive multiple of 16, got %r" % (hl_bytes,))
+    if not cfg.health.canaryMinHostGbps >= 0:
+        raise ConfigError("health.canaryMinHostGbps must be >= 0 (0 = no floor)")
     if cfg.sharing.replicas < 1:
         raise ConfigError("sharing.replicas must be >= 1")
     if cfg.health.canaryOnPreStart and cfg.sharing.replicas > 1:

@@ -138,7 +138,9 @@ FAMILIES = (
            "(wrong words of the per-XCD L2 march), xcd (wrong words of the cross-XCD exchange), atomic (wrong elements "
            "of the global-atomic tables); xcd_unreached = (writer, reader) XCD pairs the exchange did not cover (not "
            "a failure); reg (wrong words of the vector register file march, VGPRs and AGPRs), l1 (wrong words "
-           "re-read through a CU's vector L1)"),
+           "re-read through a CU's vector L1); with health.canaryHostLink also host_read, host_write (wrong words a "
+           "kernel read from / wrote to pinned host memory), host_copy (wrong words after a hipMemcpy in either "
+           "direction), host_atomic (wrong elements of the system-scope atomic tables)"),
     Family("amdgpu_canary_hbm_gbps", "gauge", ("gpu", "partition", "direction"), "manager",
            "HBM bandwidth of the last run: write, read (read + verify)"),
     Family("amdgpu_canary_matrix_tflops", "gauge", ("gpu", "partition", "path"), "manager",
@@ -152,7 +154,16 @@ FAMILIES = (
            "Multi-GPU pods whose devices span the GPU pair, sharing its xGMI link (the allocator steers new pods off it)"),
 )
 
-BY_NAME = {f.name: f for f in FAMILIES}
+# Families that only an opt-in check produces: documented and known to family_of() like the
+# others, but a node with the option off exposes none of them, so the live-exporter test does
+# not expect them.
+OPT_IN_FAMILIES = (
+    Family("amdgpu_canary_host_gbps", "gauge", ("gpu", "partition", "path"), "manager",
+           "Host-link rate of the last run (health.canaryHostLink only): kernel_read, kernel_write (kernels on "
+           "pinned host memory), copy_h2d, copy_d2h (hipMemcpy); 63 GB/s is the link's nominal rate"),
+)
+
+BY_NAME = {f.name: f for f in FAMILIES + OPT_IN_FAMILIES}
 
 
 def family_of(sample_name: str) -> Family | None:
@@ -193,7 +204,7 @@ def markdown() -> str:
            "`tests/test_topology_model.py` checks this list against a live exporter in both",
            "directions.", "",
            "| Family | Type | Labels | Source | Meaning |", "|---|---|---|---|---|"]
-    for f in FAMILIES:
+    for f in FAMILIES + OPT_IN_FAMILIES:
         out.append("| `%s` | %s | %s | %s | %s |" % (f.name, f.type, ", ".join("`%s`" % x for x in f.labels) or "—",
                                                   f.source, f.help))
     out += ["", "## PromQL examples", ""]

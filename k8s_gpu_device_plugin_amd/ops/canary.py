@@ -14,7 +14,9 @@ long-lived plugin daemon never creates a HIP context on GPUs it hands to pods.
 
 CLI: ``python -m k8s_gpu_device_plugin_amd.ops.canary --device 0 [--bytes N]`` prints
 one JSON line; ``--sites`` prints the site probe's coverage map instead, ``--fabric`` the
-fabric check's per-XCD tables, ``--cu`` the CU memory check's per-site table.  Missing
+fabric check's per-XCD tables, ``--cu`` the CU memory check's per-site table, ``--host-link``
+the host-link check (``ops/hostlink.py``: PCIe reads, writes, copies and system atomics), which
+``--with-host-link`` / ``run(host_link=True)`` merges into the full run.  Missing
 library => loud ``RuntimeError`` (never a silent pass).
 """
 from __future__ import annotations
@@ -94,6 +96,8 @@ class FabricResult(ctypes.Structure):
 
 
 CU_INJECT = ("vgpr", "agpr", "l1")
+# the rates the host-link check (ops/hostlink.py) merges into run()'s result
+HOST_LINK_RATES = ("kernel_read_gbps", "kernel_write_gbps", "copy_h2d_gbps", "copy_d2h_gbps")
 
 
 class CuSlot(ctypes.Structure):
@@ -210,7 +214,8 @@ def device_count() -> int:
     return load().amdgpu_canary_device_count()
 
 
-def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: int = 8192) -> dict:
+def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: int = 8192, host_link: bool = False,
+        host_link_bytes: int = 64 << 20) -> dict:
     r = CanaryResult()
     rc = load().amdgpu_canary_run(int(device), int(hbm_bytes), int(passes), int(mfma_iters), ctypes.byref(r))
     out = {f[0]: getattr(r, f[0]) for f in CanaryResult._fields_}
@@ -235,7 +240,31 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     if out["reg_errors"] or out["l1_errors"]:
         out["ok"] = False
         out["error"] = out["error"] or cu["error"]
+    if host_link:
+        _merge_host_link(out, device, host_link_bytes)
     return out
+
+
+def _merge_host_link(out: dict, device: int, nbytes: int) -> None:
+    """The host-link check (``ops/hostlink.py``, a library of its own), same process and
+    device, merged into ``run``'s verdict the way the CU memory check is."""
+    from . import hostlink
+    try:
+        hl = hostlink.host_link_check(device, nbytes)
+    except (RuntimeError, OSError) as e:
+        out["ok"] = False
+        out["error"] = out["error"] or str(e)
+        return
+    out["host_read_errors"] = hl["read_errors"]
+    out["host_write_errors"] = hl["write_errors"]
+    out["host_copy_errors"] = hl["h2d_errors"] + hl["d2h_errors"]
+    out["host_atomic_errors"] = hl["atomic_errors"]
+    for rate in HOST_LINK_RATES:
+        out[rate] = hl[rate]
+    out["host_ms"] = hl["ms"]
+    if not hl["ok"]:
+        out["ok"] = False
+        out["error"] = out["error"] or hl["error"]
 
 
 def cu_check(device: int = 0, blocks: int = 0, reps: int = 2, l1_kb: int = 16, l1_reps: int = 4, inject=None,
@@ -590,10 +619,13 @@ def abft(a_bf16_bits, bt_bf16_bits, c, device: int = 0) -> tuple:
     return int(rows.value), int(cols.value)
 
 
-def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0, passes: int = 1) -> dict:
+def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0, passes: int = 1,
+                 host_link: bool = False, host_link_bytes: int = 64 << 20) -> dict:
     """``run`` in a child process (its own HIP runtime, gone when it exits)."""
     cmd = [sys.executable, "-m", "k8s_gpu_device_plugin_amd.ops.canary", "--device", str(device),
            "--bytes", str(hbm_bytes), "--passes", str(passes)]
+    if host_link:
+        cmd += ["--with-host-link", "--host-link-bytes", str(host_link_bytes)]
     env = dict(os.environ)
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
@@ -629,7 +661,16 @@ def main(argv=None) -> int:
                     help="only the fabric check: L2 march, cross-XCD exchange, global atomics")
     ap.add_argument("--cu", action="store_true",
                     help="only the CU memory check: register-file march and L1 march, per site")
+    ap.add_argument("--host-link", action="store_true",
+                    help="only the host-link check: PCIe reads, writes, copies and system atomics")
+    ap.add_argument("--with-host-link", action="store_true", help="the full run, with the host-link check merged in")
+    ap.add_argument("--host-link-bytes", type=int, default=64 << 20)
     a = ap.parse_args(argv)
+    if a.host_link:
+        from . import hostlink
+        res = hostlink.host_link_check(a.device, a.host_link_bytes)
+        print(json.dumps(res))
+        return 0 if res["ok"] else 1
     if a.cu:
         res = cu_check(a.device)
         print(json.dumps(res))
@@ -648,7 +689,8 @@ def main(argv=None) -> int:
                         random_data=a.gemm_random)
         print(json.dumps(res))
         return 0 if not res["errors"] else 1
-    res = run(a.device, a.bytes, a.passes, a.mfma_iters)
+    res = run(a.device, a.bytes, a.passes, a.mfma_iters, host_link=a.with_host_link,
+              host_link_bytes=a.host_link_bytes)
     print(json.dumps(res))
     return 0 if res["ok"] else 1
 

@@ -1397,8 +1397,12 @@ class PluginManager:
         ``hw_part``): applies the configured performance floors and records the result for
         /metrics.  Thread-safe; runs on canary pool threads."""
         from ..ops import canary
-        res = dict(canary.run_isolated(max(0, hip), self.cfg.health.canaryBytes, self.cfg.health.canaryTimeoutS))
         h = self.cfg.health
+        if h.canaryHostLink:
+            res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS, host_link=True,
+                                           host_link_bytes=h.canaryHostLinkBytes))
+        else:
+            res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS))
         if res.get("ok"):
             low = []
             hbm = min(res.get("write_gbps", 0.0), res.get("read_gbps", 0.0))
@@ -1406,6 +1410,10 @@ class PluginManager:
                 low.append("HBM %.0f GB/s < %.0f" % (hbm, h.canaryMinHbmGbps))
             if h.canaryMinTflops > 0 and res.get("mfma_tflops", 0.0) < h.canaryMinTflops:
                 low.append("bf16 MFMA %.0f TFLOP/s < %.0f" % (res.get("mfma_tflops", 0.0), h.canaryMinTflops))
+            if h.canaryHostLink and h.canaryMinHostGbps > 0:
+                host = min(res.get(k, 0.0) for k in canary.HOST_LINK_RATES)  # the slowest of the four paths
+                if host < h.canaryMinHostGbps:
+                    low.append("host link %.0f GB/s < %.0f" % (host, h.canaryMinHostGbps))
             if low:
                 res["ok"] = False
                 res["error"] = "below the canary performance floor: " + ", ".join(low)
@@ -1596,7 +1604,8 @@ class PluginManager:
                 ("amdgpu_canary_last_ok", "1 if the last canary run passed."),
                 ("amdgpu_canary_errors", "Mismatches found by the last canary run, per check."),
                 ("amdgpu_canary_hbm_gbps", "HBM bandwidth measured by the last canary run."),
-                ("amdgpu_canary_matrix_tflops", "Dense matrix-core rate measured by the last canary run."))
+                ("amdgpu_canary_matrix_tflops", "Dense matrix-core rate measured by the last canary run."),
+                ("amdgpu_canary_host_gbps", "Host-link rate measured by the last canary run, per path."))
         rows = {name: [] for name, _ in fams}
         for (gpu, part), (t, r) in runs:
             lab = 'gpu="%d",partition="%d"' % (gpu, part)
@@ -1606,7 +1615,9 @@ class PluginManager:
                                ("lowp", "lowp_errors"), ("lds", "lds_errors"), ("site", "site_errors"),
                                ("unreached", "cus_unreached"), ("l2", "l2_errors"), ("xcd", "xcd_errors"),
                                ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
-                               ("reg", "reg_errors"), ("l1", "l1_errors")):
+                               ("reg", "reg_errors"), ("l1", "l1_errors"), ("host_read", "host_read_errors"),
+                               ("host_write", "host_write_errors"), ("host_copy", "host_copy_errors"),
+                               ("host_atomic", "host_atomic_errors")):
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
@@ -1616,6 +1627,9 @@ class PluginManager:
                               ("mxfp4", "fp4_tflops")):
                 if key in r:
                     rows["amdgpu_canary_matrix_tflops"].append('{%s,path="%s"} %.1f' % (lab, path, float(r[key])))
+            for path in ("kernel_read", "kernel_write", "copy_h2d", "copy_d2h"):
+                if path + "_gbps" in r:
+                    rows["amdgpu_canary_host_gbps"].append('{%s,path="%s"} %.1f' % (lab, path, float(r[path + "_gbps"])))
         out = []
         for name, help_ in fams:
             if rows[name]:
