@@ -8,6 +8,8 @@ the repo snapshot to the GPU box):
   ``hipcc --offload-arch=gfx950``.
 * ``k8s_gpu_device_plugin_amd/ops/hostlink/libamdgpu_hostlink.so``  the canary's host-link
   check (PCIe reads, writes, copies, system atomics), same ``hipcc`` line.
+* ``k8s_gpu_device_plugin_amd/ops/pace/libamdgpu_pace.so``  the canary's pace check
+  (in-kernel clock and rate per XCD, CU and SIMD), same ``hipcc`` line.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -73,6 +75,11 @@ HOSTLINK_DIR = os.path.join(PKG_DIR, "ops", "hostlink")
 HOSTLINK_SOURCES = [os.path.join(HOSTLINK_DIR, "hostlink.hip")]
 HOSTLINK_HEADERS = [os.path.join(HOSTLINK_DIR, f) for f in ("hostlink.h", "hostlink_host.h")] + CANARY_HEADERS
 HOSTLINK_LIB = os.path.join(HOSTLINK_DIR, "libamdgpu_hostlink.so")
+# the pace check (in-kernel clock and rate per XCD, CU and SIMD): the same arrangement
+PACE_DIR = os.path.join(PKG_DIR, "ops", "pace")
+PACE_SOURCES = [os.path.join(PACE_DIR, "pace.hip")]
+PACE_HEADERS = [os.path.join(PACE_DIR, f) for f in ("pace.h", "pace_host.h")] + CANARY_HEADERS
+PACE_LIB = os.path.join(PACE_DIR, "libamdgpu_pace.so")
 
 
 def native_ext_path() -> str:
@@ -347,11 +354,27 @@ def build_hostlink(force: bool = False, verbose: bool = True) -> str:
     return HOSTLINK_LIB
 
 
+def build_pace(force: bool = False, verbose: bool = True) -> str:
+    """hipcc the pace check (``ops/pace/``) for gfx950 only, as ``build_canary`` does."""
+    hipcc = hipcc_path()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
+    if force or _stale(PACE_LIB, PACE_SOURCES + PACE_HEADERS):
+        tmp = PACE_LIB + ".tmp"
+        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
+              "-Wall", "-o", tmp] + PACE_SOURCES, "hipcc pace")
+        os.replace(tmp, PACE_LIB)
+        if verbose:
+            print("built", os.path.relpath(PACE_LIB, ROOT))
+    return PACE_LIB
+
+
 def build_all(force: bool = False) -> None:
     build_native(force=force)
     build_bench(force=force)
     build_canary(force=force)
     build_hostlink(force=force)
+    build_pace(force=force)
 
 
 def main(argv=None) -> int:
@@ -389,6 +412,7 @@ def main(argv=None) -> int:
     if not args.no_canary:
         build_canary(force=args.force)
         build_hostlink(force=args.force)
+        build_pace(force=args.force)
     return 0
 
 

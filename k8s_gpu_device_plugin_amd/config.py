@@ -95,6 +95,12 @@ class HealthConfig:
     canaryHostLink: bool = False
     canaryHostLinkBytes: int = 64 << 20
     canaryMinHostGbps: float = 0.0
+    # the canary's pace check (in-kernel clock and rate per XCD, CU and SIMD) in every run, and
+    # its floors (0 = off): the clock of the slowest XCD in MHz, and how far the slowest XCD
+    # may lag the median over XCDs (the smaller of the clock and the memory-time ratio, in [0, 1])
+    canaryPace: bool = False
+    canaryMinClockMhz: float = 0.0
+    canaryMinXcdPaceRatio: float = 0.0
     rejectUnhealthyAllocate: bool = True
     # retired + pending HBM pages at which a GPU goes Unhealthy: 0 = the GPU's own RAS
     # threshold when readable (root), -1 = never, N > 0 = N
@@ -400,6 +406,10 @@ def validate(cfg: Config) -> Config:
         raise ConfigError("health.canaryHostLinkBytes must be a positive multiple of 16, got %r" % (hl_bytes,))
     if not cfg.health.canaryMinHostGbps >= 0:
         raise ConfigError("health.canaryMinHostGbps must be >= 0 (0 = no floor)")
+    if not cfg.health.canaryMinClockMhz >= 0:
+        raise ConfigError("health.canaryMinClockMhz must be >= 0 (0 = no floor)")
+    if not 0 <= cfg.health.canaryMinXcdPaceRatio <= 1:
+        raise ConfigError("health.canaryMinXcdPaceRatio must lie in [0, 1] (0 = no floor)")
     if cfg.sharing.replicas < 1:
         raise ConfigError("sharing.replicas must be >= 1")
     if cfg.health.canaryOnPreStart and cfg.sharing.replicas > 1:

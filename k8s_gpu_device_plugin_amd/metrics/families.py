@@ -140,7 +140,8 @@ FAMILIES = (
            "a failure); reg (wrong words of the vector register file march, VGPRs and AGPRs), l1 (wrong words "
            "re-read through a CU's vector L1); with health.canaryHostLink also host_read, host_write (wrong words a "
            "kernel read from / wrote to pinned host memory), host_copy (wrong words after a hipMemcpy in either "
-           "direction), host_atomic (wrong elements of the system-scope atomic tables)"),
+           "direction), host_atomic (wrong elements of the system-scope atomic tables); with health.canaryPace also "
+           "pace (wrong results of the pace check's MFMA loop and wrong words its memory stage read)"),
     Family("amdgpu_canary_hbm_gbps", "gauge", ("gpu", "partition", "direction"), "manager",
            "HBM bandwidth of the last run: write, read (read + verify)"),
     Family("amdgpu_canary_matrix_tflops", "gauge", ("gpu", "partition", "path"), "manager",
@@ -161,6 +162,12 @@ OPT_IN_FAMILIES = (
     Family("amdgpu_canary_host_gbps", "gauge", ("gpu", "partition", "path"), "manager",
            "Host-link rate of the last run (health.canaryHostLink only): kernel_read, kernel_write (kernels on "
            "pinned host memory), copy_h2d, copy_d2h (hipMemcpy); 63 GB/s is the link's nominal rate"),
+    Family("amdgpu_canary_clock_mhz", "gauge", ("gpu", "partition", "stat"), "manager",
+           "Shader clock measured inside the pace check's kernels in the last run (health.canaryPace only): min, max "
+           "over the partition's XCDs; the clock held during a burst of under a millisecond, not a sustained one"),
+    Family("amdgpu_canary_xcd_pace_ratio", "gauge", ("gpu", "partition", "path"), "manager",
+           "Slowest XCD against the median over XCDs in the last run (health.canaryPace only): clock (in-kernel shader "
+           "clock), mem (time to stream the same bytes from memory); 1 when balanced, below 1 when one XCD lags"),
 )
 
 BY_NAME = {f.name: f for f in FAMILIES + OPT_IN_FAMILIES}

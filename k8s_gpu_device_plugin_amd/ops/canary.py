@@ -16,8 +16,10 @@ CLI: ``python -m k8s_gpu_device_plugin_amd.ops.canary --device 0 [--bytes N]`` p
 one JSON line; ``--sites`` prints the site probe's coverage map instead, ``--fabric`` the
 fabric check's per-XCD tables, ``--cu`` the CU memory check's per-site table, ``--host-link``
 the host-link check (``ops/hostlink.py``: PCIe reads, writes, copies and system atomics), which
-``--with-host-link`` / ``run(host_link=True)`` merges into the full run.  Missing
-library => loud ``RuntimeError`` (never a silent pass).
+``--with-host-link`` / ``run(host_link=True)`` merges into the full run, ``--pace`` the pace
+check (``ops/pace.py``: in-kernel clock and rate per XCD, CU and SIMD), which ``--with-pace`` /
+``run(pace=True)`` merges likewise.  Missing library => loud ``RuntimeError`` (never a silent
+pass).
 """
 from __future__ import annotations
 
@@ -98,6 +100,8 @@ class FabricResult(ctypes.Structure):
 CU_INJECT = ("vgpr", "agpr", "l1")
 # the rates the host-link check (ops/hostlink.py) merges into run()'s result
 HOST_LINK_RATES = ("kernel_read_gbps", "kernel_write_gbps", "copy_h2d_gbps", "copy_d2h_gbps")
+# what the pace check (ops/pace.py) merges into run()'s result under the same name
+PACE_KEYS = ("pace_errors", "clock_mhz_min", "clock_mhz_max", "clock_fraction", "xcd_pace_ratio", "xcd_mem_ratio")
 
 
 class CuSlot(ctypes.Structure):
@@ -215,7 +219,7 @@ def device_count() -> int:
 
 
 def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: int = 8192, host_link: bool = False,
-        host_link_bytes: int = 64 << 20) -> dict:
+        host_link_bytes: int = 64 << 20, pace: bool = False) -> dict:
     r = CanaryResult()
     rc = load().amdgpu_canary_run(int(device), int(hbm_bytes), int(passes), int(mfma_iters), ctypes.byref(r))
     out = {f[0]: getattr(r, f[0]) for f in CanaryResult._fields_}
@@ -240,9 +244,32 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     if out["reg_errors"] or out["l1_errors"]:
         out["ok"] = False
         out["error"] = out["error"] or cu["error"]
+    if pace:
+        _merge_pace(out, device)
     if host_link:
         _merge_host_link(out, device, host_link_bytes)
     return out
+
+
+def _merge_pace(out: dict, device: int) -> None:
+    """The pace check (``ops/pace.py``, a library of its own), same process and device.  Wrong
+    results fail the run; slowness is carried as figures and ``pace_note`` for the caller's floors."""
+    from . import pace as pace_mod
+    try:
+        p = pace_mod.pace_check(device)
+    except (RuntimeError, OSError) as e:
+        out["ok"] = False
+        out["error"] = out["error"] or str(e)
+        return
+    for key in PACE_KEYS:
+        out[key] = p[key]
+    out["pace_slow_sites"] = p["slow_sites"]
+    out["pace_slow_xccs"] = p["slow_xccs"]
+    out["pace_ms"] = p["ms"]
+    out["pace_note"] = p["note"]
+    if not p["ok"]:
+        out["ok"] = False
+        out["error"] = out["error"] or p["error"]
 
 
 def _merge_host_link(out: dict, device: int, nbytes: int) -> None:
@@ -620,12 +647,14 @@ def abft(a_bf16_bits, bt_bf16_bits, c, device: int = 0) -> tuple:
 
 
 def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0, passes: int = 1,
-                 host_link: bool = False, host_link_bytes: int = 64 << 20) -> dict:
+                 host_link: bool = False, host_link_bytes: int = 64 << 20, pace: bool = False) -> dict:
     """``run`` in a child process (its own HIP runtime, gone when it exits)."""
     cmd = [sys.executable, "-m", "k8s_gpu_device_plugin_amd.ops.canary", "--device", str(device),
            "--bytes", str(hbm_bytes), "--passes", str(passes)]
     if host_link:
         cmd += ["--with-host-link", "--host-link-bytes", str(host_link_bytes)]
+    if pace:
+        cmd += ["--with-pace"]
     env = dict(os.environ)
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
@@ -665,7 +694,15 @@ def main(argv=None) -> int:
                     help="only the host-link check: PCIe reads, writes, copies and system atomics")
     ap.add_argument("--with-host-link", action="store_true", help="the full run, with the host-link check merged in")
     ap.add_argument("--host-link-bytes", type=int, default=64 << 20)
+    ap.add_argument("--pace", action="store_true",
+                    help="only the pace check: in-kernel clock and rate per XCD, CU and SIMD")
+    ap.add_argument("--with-pace", action="store_true", help="the full run, with the pace check merged in")
     a = ap.parse_args(argv)
+    if a.pace:
+        from . import pace as pace_mod
+        res = pace_mod.pace_check(a.device)
+        print(json.dumps(res))
+        return 0 if res["ok"] else 1
     if a.host_link:
         from . import hostlink
         res = hostlink.host_link_check(a.device, a.host_link_bytes)
@@ -689,8 +726,9 @@ def main(argv=None) -> int:
                         random_data=a.gemm_random)
         print(json.dumps(res))
         return 0 if not res["errors"] else 1
+    more = {"pace": True} if a.with_pace else {}  # passed only when asked for
     res = run(a.device, a.bytes, a.passes, a.mfma_iters, host_link=a.with_host_link,
-              host_link_bytes=a.host_link_bytes)
+              host_link_bytes=a.host_link_bytes, **more)
     print(json.dumps(res))
     return 0 if res["ok"] else 1
 

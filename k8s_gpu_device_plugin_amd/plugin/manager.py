@@ -1398,11 +1398,12 @@ class PluginManager:
         /metrics.  Thread-safe; runs on canary pool threads."""
         from ..ops import canary
         h = self.cfg.health
+        more = {}  # each option's keywords only when it is on
         if h.canaryHostLink:
-            res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS, host_link=True,
-                                           host_link_bytes=h.canaryHostLinkBytes))
-        else:
-            res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS))
+            more.update(host_link=True, host_link_bytes=h.canaryHostLinkBytes)
+        if h.canaryPace:
+            more["pace"] = True
+        res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS, **more))
         if res.get("ok"):
             low = []
             hbm = min(res.get("write_gbps", 0.0), res.get("read_gbps", 0.0))
@@ -1414,6 +1415,12 @@ class PluginManager:
                 host = min(res.get(k, 0.0) for k in canary.HOST_LINK_RATES)  # the slowest of the four paths
                 if host < h.canaryMinHostGbps:
                     low.append("host link %.0f GB/s < %.0f" % (host, h.canaryMinHostGbps))
+            if h.canaryPace and h.canaryMinClockMhz > 0 and res.get("clock_mhz_min", 0.0) < h.canaryMinClockMhz:
+                low.append("clock %.0f MHz < %.0f" % (res.get("clock_mhz_min", 0.0), h.canaryMinClockMhz))
+            if h.canaryPace and h.canaryMinXcdPaceRatio > 0:
+                lag = min(res.get("xcd_pace_ratio", 0.0), res.get("xcd_mem_ratio", 0.0))  # the worse of the two
+                if lag < h.canaryMinXcdPaceRatio:
+                    low.append("slowest XCD at %.2f of the median < %g" % (lag, h.canaryMinXcdPaceRatio))
             if low:
                 res["ok"] = False
                 res["error"] = "below the canary performance floor: " + ", ".join(low)
@@ -1605,7 +1612,9 @@ class PluginManager:
                 ("amdgpu_canary_errors", "Mismatches found by the last canary run, per check."),
                 ("amdgpu_canary_hbm_gbps", "HBM bandwidth measured by the last canary run."),
                 ("amdgpu_canary_matrix_tflops", "Dense matrix-core rate measured by the last canary run."),
-                ("amdgpu_canary_host_gbps", "Host-link rate measured by the last canary run, per path."))
+                ("amdgpu_canary_host_gbps", "Host-link rate measured by the last canary run, per path."),
+                ("amdgpu_canary_clock_mhz", "In-kernel shader clock of the last canary run: slowest and fastest XCD."),
+                ("amdgpu_canary_xcd_pace_ratio", "Slowest XCD against the median over XCDs in the last canary run."))
         rows = {name: [] for name, _ in fams}
         for (gpu, part), (t, r) in runs:
             lab = 'gpu="%d",partition="%d"' % (gpu, part)
@@ -1617,7 +1626,7 @@ class PluginManager:
                                ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
                                ("reg", "reg_errors"), ("l1", "l1_errors"), ("host_read", "host_read_errors"),
                                ("host_write", "host_write_errors"), ("host_copy", "host_copy_errors"),
-                               ("host_atomic", "host_atomic_errors")):
+                               ("host_atomic", "host_atomic_errors"), ("pace", "pace_errors")):
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
@@ -1630,6 +1639,12 @@ class PluginManager:
             for path in ("kernel_read", "kernel_write", "copy_h2d", "copy_d2h"):
                 if path + "_gbps" in r:
                     rows["amdgpu_canary_host_gbps"].append('{%s,path="%s"} %.1f' % (lab, path, float(r[path + "_gbps"])))
+            for stat in ("min", "max"):
+                if "clock_mhz_" + stat in r:
+                    rows["amdgpu_canary_clock_mhz"].append('{%s,stat="%s"} %.0f' % (lab, stat, float(r["clock_mhz_" + stat])))
+            for path, key in (("clock", "xcd_pace_ratio"), ("mem", "xcd_mem_ratio")):
+                if key in r:
+                    rows["amdgpu_canary_xcd_pace_ratio"].append('{%s,path="%s"} %.3f' % (lab, path, float(r[key])))
         out = []
         for name, help_ in fams:
             if rows[name]:
