@@ -10,6 +10,8 @@ the repo snapshot to the GPU box):
   check (PCIe reads, writes, copies, system atomics), same ``hipcc`` line.
 * ``k8s_gpu_device_plugin_amd/ops/pace/libamdgpu_pace.so``  the canary's pace check
   (in-kernel clock and rate per XCD, CU and SIMD), same ``hipcc`` line.
+* ``k8s_gpu_device_plugin_amd/ops/ldspath/libamdgpu_ldspath.so``  the canary's LDS-path check
+  (LDS widths and atomics, lane swaps, the transposed read), same ``hipcc`` line.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -80,6 +82,11 @@ PACE_DIR = os.path.join(PKG_DIR, "ops", "pace")
 PACE_SOURCES = [os.path.join(PACE_DIR, "pace.hip")]
 PACE_HEADERS = [os.path.join(PACE_DIR, f) for f in ("pace.h", "pace_host.h")] + CANARY_HEADERS
 PACE_LIB = os.path.join(PACE_DIR, "libamdgpu_pace.so")
+# the LDS-path check (LDS widths and atomics, lane swaps, the transposed read): likewise
+LDSPATH_DIR = os.path.join(PKG_DIR, "ops", "ldspath")
+LDSPATH_SOURCES = [os.path.join(LDSPATH_DIR, "ldspath.hip")]
+LDSPATH_HEADERS = [os.path.join(LDSPATH_DIR, f) for f in ("ldspath.h", "ldspath_host.h")] + CANARY_HEADERS
+LDSPATH_LIB = os.path.join(LDSPATH_DIR, "libamdgpu_ldspath.so")
 
 
 def native_ext_path() -> str:
@@ -369,12 +376,28 @@ def build_pace(force: bool = False, verbose: bool = True) -> str:
     return PACE_LIB
 
 
+def build_ldspath(force: bool = False, verbose: bool = True) -> str:
+    """hipcc the LDS-path check (``ops/ldspath/``) for gfx950 only, as ``build_canary`` does."""
+    hipcc = hipcc_path()
+    if hipcc is None:
+        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
+    if force or _stale(LDSPATH_LIB, LDSPATH_SOURCES + LDSPATH_HEADERS):
+        tmp = LDSPATH_LIB + ".tmp"
+        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
+              "-Wall", "-o", tmp] + LDSPATH_SOURCES, "hipcc ldspath")
+        os.replace(tmp, LDSPATH_LIB)
+        if verbose:
+            print("built", os.path.relpath(LDSPATH_LIB, ROOT))
+    return LDSPATH_LIB
+
+
 def build_all(force: bool = False) -> None:
     build_native(force=force)
     build_bench(force=force)
     build_canary(force=force)
     build_hostlink(force=force)
     build_pace(force=force)
+    build_ldspath(force=force)
 
 
 def main(argv=None) -> int:
@@ -413,6 +436,7 @@ def main(argv=None) -> int:
         build_canary(force=args.force)
         build_hostlink(force=args.force)
         build_pace(force=args.force)
+        build_ldspath(force=args.force)
     return 0
 
 

@@ -101,6 +101,9 @@ class HealthConfig:
     canaryPace: bool = False
     canaryMinClockMhz: float = 0.0
     canaryMinXcdPaceRatio: float = 0.0
+    # the canary's LDS-path check (LDS widths, atomics and transposed read per CU, every
+    # lane-crossing instruction per SIMD) in every run; it measures no rate, so it has no floor
+    canaryLdsPath: bool = False
     rejectUnhealthyAllocate: bool = True
     # retired + pending HBM pages at which a GPU goes Unhealthy: 0 = the GPU's own RAS
     # threshold when readable (root), -1 = never, N > 0 = N

@@ -141,7 +141,10 @@ FAMILIES = (
            "re-read through a CU's vector L1); with health.canaryHostLink also host_read, host_write (wrong words a "
            "kernel read from / wrote to pinned host memory), host_copy (wrong words after a hipMemcpy in either "
            "direction), host_atomic (wrong elements of the system-scope atomic tables); with health.canaryPace also "
-           "pace (wrong results of the pace check's MFMA loop and wrong words its memory stage read)"),
+           "pace (wrong results of the pace check's MFMA loop and wrong words its memory stage read); with "
+           "health.canaryLdsPath also lds_width (wrong words of the LDS march at every access width), lds_dma (wrong "
+           "words after the LDS-DMA fill), lds_atomic (wrong elements of the LDS-atomic tables), lane (wrong words of "
+           "the lane-crossing instructions), lds_tr (wrong elements of the transposed LDS read)"),
     Family("amdgpu_canary_hbm_gbps", "gauge", ("gpu", "partition", "direction"), "manager",
            "HBM bandwidth of the last run: write, read (read + verify)"),
     Family("amdgpu_canary_matrix_tflops", "gauge", ("gpu", "partition", "path"), "manager",

@@ -18,7 +18,9 @@ fabric check's per-XCD tables, ``--cu`` the CU memory check's per-site table, ``
 the host-link check (``ops/hostlink.py``: PCIe reads, writes, copies and system atomics), which
 ``--with-host-link`` / ``run(host_link=True)`` merges into the full run, ``--pace`` the pace
 check (``ops/pace.py``: in-kernel clock and rate per XCD, CU and SIMD), which ``--with-pace`` /
-``run(pace=True)`` merges likewise.  Missing library => loud ``RuntimeError`` (never a silent
+``run(pace=True)`` merges likewise, ``--lds-path`` the LDS-path check (``ops/ldspath.py``: LDS
+widths, atomics and transposed read per CU, every lane-crossing instruction per SIMD), which
+``--with-lds-path`` / ``run(lds_path=True)`` merges likewise.  Missing library => loud ``RuntimeError`` (never a silent
 pass).
 """
 from __future__ import annotations
@@ -100,6 +102,10 @@ class FabricResult(ctypes.Structure):
 CU_INJECT = ("vgpr", "agpr", "l1")
 # the rates the host-link check (ops/hostlink.py) merges into run()'s result
 HOST_LINK_RATES = ("kernel_read_gbps", "kernel_write_gbps", "copy_h2d_gbps", "copy_d2h_gbps")
+# what the LDS-path check (ops/ldspath.py) merges into run()'s result: (key there, key of ldspath_check)
+LDS_PATH_KEYS = (("ldspath_errors", "ldspath_errors"), ("lds_width_errors", "lds_errors"), ("lds_dma_errors", "dma_errors"),
+                 ("lds_atomic_errors", "lds_atomic_errors"), ("lane_errors", "lane_errors"), ("tr_errors", "tr_errors"),
+                 ("ldspath_ms", "ms"), ("ldspath_bad_sites", "bad_sites"))
 # what the pace check (ops/pace.py) merges into run()'s result under the same name
 PACE_KEYS = ("pace_errors", "clock_mhz_min", "clock_mhz_max", "clock_fraction", "xcd_pace_ratio", "xcd_mem_ratio")
 
@@ -219,7 +225,7 @@ def device_count() -> int:
 
 
 def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: int = 8192, host_link: bool = False,
-        host_link_bytes: int = 64 << 20, pace: bool = False) -> dict:
+        host_link_bytes: int = 64 << 20, pace: bool = False, lds_path: bool = False) -> dict:
     r = CanaryResult()
     rc = load().amdgpu_canary_run(int(device), int(hbm_bytes), int(passes), int(mfma_iters), ctypes.byref(r))
     out = {f[0]: getattr(r, f[0]) for f in CanaryResult._fields_}
@@ -244,11 +250,30 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     if out["reg_errors"] or out["l1_errors"]:
         out["ok"] = False
         out["error"] = out["error"] or cu["error"]
+    if lds_path:
+        _merge_lds_path(out, device)
     if pace:
         _merge_pace(out, device)
     if host_link:
         _merge_host_link(out, device, host_link_bytes)
     return out
+
+
+def _merge_lds_path(out: dict, device: int) -> None:
+    """The LDS-path check (``ops/ldspath.py``, a library of its own), same process and device.
+    ``lds_errors`` is already ``lds_march``'s count, so the width passes' is ``lds_width_errors``."""
+    from . import ldspath
+    try:
+        p = ldspath.ldspath_check(device)
+    except (RuntimeError, OSError) as e:
+        out["ok"] = False
+        out["error"] = out["error"] or str(e)
+        return
+    for key, theirs in LDS_PATH_KEYS:
+        out[key] = p[theirs]
+    if not p["ok"]:
+        out["ok"] = False
+        out["error"] = out["error"] or p["error"]
 
 
 def _merge_pace(out: dict, device: int) -> None:
@@ -647,7 +672,8 @@ def abft(a_bf16_bits, bt_bf16_bits, c, device: int = 0) -> tuple:
 
 
 def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0, passes: int = 1,
-                 host_link: bool = False, host_link_bytes: int = 64 << 20, pace: bool = False) -> dict:
+                 host_link: bool = False, host_link_bytes: int = 64 << 20, pace: bool = False,
+                 lds_path: bool = False) -> dict:
     """``run`` in a child process (its own HIP runtime, gone when it exits)."""
     cmd = [sys.executable, "-m", "k8s_gpu_device_plugin_amd.ops.canary", "--device", str(device),
            "--bytes", str(hbm_bytes), "--passes", str(passes)]
@@ -655,6 +681,8 @@ def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0
         cmd += ["--with-host-link", "--host-link-bytes", str(host_link_bytes)]
     if pace:
         cmd += ["--with-pace"]
+    if lds_path:
+        cmd += ["--with-lds-path"]
     env = dict(os.environ)
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
@@ -697,7 +725,15 @@ def main(argv=None) -> int:
     ap.add_argument("--pace", action="store_true",
                     help="only the pace check: in-kernel clock and rate per XCD, CU and SIMD")
     ap.add_argument("--with-pace", action="store_true", help="the full run, with the pace check merged in")
+    ap.add_argument("--lds-path", action="store_true",
+                    help="only the LDS-path check: LDS widths, atomics, lane swaps and the transposed read, per site")
+    ap.add_argument("--with-lds-path", action="store_true", help="the full run, with the LDS-path check merged in")
     a = ap.parse_args(argv)
+    if a.lds_path:
+        from . import ldspath
+        res = ldspath.ldspath_check(a.device)
+        print(json.dumps(res))
+        return 0 if res["ok"] else 1
     if a.pace:
         from . import pace as pace_mod
         res = pace_mod.pace_check(a.device)
@@ -727,6 +763,8 @@ def main(argv=None) -> int:
         print(json.dumps(res))
         return 0 if not res["errors"] else 1
     more = {"pace": True} if a.with_pace else {}  # passed only when asked for
+    if a.with_lds_path:
+        more["lds_path"] = True
     res = run(a.device, a.bytes, a.passes, a.mfma_iters, host_link=a.with_host_link,
               host_link_bytes=a.host_link_bytes, **more)
     print(json.dumps(res))

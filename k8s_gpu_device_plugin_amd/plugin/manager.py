@@ -1403,6 +1403,8 @@ class PluginManager:
             more.update(host_link=True, host_link_bytes=h.canaryHostLinkBytes)
         if h.canaryPace:
             more["pace"] = True
+        if h.canaryLdsPath:
+            more["lds_path"] = True
         res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS, **more))
         if res.get("ok"):
             low = []
@@ -1626,7 +1628,9 @@ class PluginManager:
                                ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
                                ("reg", "reg_errors"), ("l1", "l1_errors"), ("host_read", "host_read_errors"),
                                ("host_write", "host_write_errors"), ("host_copy", "host_copy_errors"),
-                               ("host_atomic", "host_atomic_errors"), ("pace", "pace_errors")):
+                               ("host_atomic", "host_atomic_errors"), ("pace", "pace_errors"),
+                               ("lds_width", "lds_width_errors"), ("lds_dma", "lds_dma_errors"),
+                               ("lds_atomic", "lds_atomic_errors"), ("lane", "lane_errors"), ("lds_tr", "tr_errors")):
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
