@@ -68,25 +68,33 @@ BINDING_SOURCES = ["bindings.cpp"]
 BENCH_SOURCES = ["loadgen.cpp", "bench_bindings.cpp"]  # in HARNESS_DIR
 FUZZ_TARGETS = ("pbwire", "hpack", "grpc", "http")
 FUZZ_DIR = os.path.join(HARNESS_DIR, "fuzz")
-CANARY_SOURCES = [os.path.join(PKG_DIR, "ops", f) for f in ("canary.hip", "hbm.hip", "gemm.hip", "datapath.hip",
-                                                               "sites.hip", "fabric.hip", "cumem.hip")]
-CANARY_HEADERS = [os.path.join(PKG_DIR, "ops", f) for f in ("canary_common.h", "canary_host.h")]
-CANARY_LIB = os.path.join(PKG_DIR, "ops", "libamdgpu_canary.so")
-# the host-link check: a library of its own next to the canary's, sharing its header-only helpers
-HOSTLINK_DIR = os.path.join(PKG_DIR, "ops", "hostlink")
-HOSTLINK_SOURCES = [os.path.join(HOSTLINK_DIR, "hostlink.hip")]
-HOSTLINK_HEADERS = [os.path.join(HOSTLINK_DIR, f) for f in ("hostlink.h", "hostlink_host.h")] + CANARY_HEADERS
-HOSTLINK_LIB = os.path.join(HOSTLINK_DIR, "libamdgpu_hostlink.so")
-# the pace check (in-kernel clock and rate per XCD, CU and SIMD): the same arrangement
-PACE_DIR = os.path.join(PKG_DIR, "ops", "pace")
-PACE_SOURCES = [os.path.join(PACE_DIR, "pace.hip")]
-PACE_HEADERS = [os.path.join(PACE_DIR, f) for f in ("pace.h", "pace_host.h")] + CANARY_HEADERS
-PACE_LIB = os.path.join(PACE_DIR, "libamdgpu_pace.so")
-# the LDS-path check (LDS widths and atomics, lane swaps, the transposed read): likewise
-LDSPATH_DIR = os.path.join(PKG_DIR, "ops", "ldspath")
-LDSPATH_SOURCES = [os.path.join(LDSPATH_DIR, "ldspath.hip")]
-LDSPATH_HEADERS = [os.path.join(LDSPATH_DIR, f) for f in ("ldspath.h", "ldspath_host.h")] + CANARY_HEADERS
-LDSPATH_LIB = os.path.join(LDSPATH_DIR, "libamdgpu_ldspath.so")
+OPS_DIR = os.path.join(PKG_DIR, "ops")
+CANARY_HEADERS = [os.path.join(OPS_DIR, f) for f in ("canary_common.h", "canary_host.h", "site.h")]
+
+
+def _hip_lib(name: str, subdir: str, sources, headers):
+    """A row of ``HIP_LIBS``: ``libamdgpu_<name>.so`` from the files of ``ops/<subdir>`` and the canary's headers."""
+    d = os.path.normpath(os.path.join(OPS_DIR, subdir))
+    return {"name": name, "lib": os.path.join(d, "libamdgpu_%s.so" % name),
+            "sources": [os.path.join(d, f) for f in sources],
+            "headers": [os.path.join(d, f) for f in headers] + CANARY_HEADERS}
+
+
+# The canary's library, then each opt-in check's: a library of its own in a directory of its own,
+# sharing the canary's header-only helpers.  A new check adds one row.
+HIP_LIBS = (
+    _hip_lib("canary", "", ("canary.hip", "hbm.hip", "gemm.hip", "datapath.hip", "sites.hip", "fabric.hip",
+                            "cumem.hip"), ()),
+    _hip_lib("hostlink", "hostlink", ("hostlink.hip",), ("hostlink.h", "hostlink_host.h")),
+    _hip_lib("pace", "pace", ("pace.hip",), ("pace.h", "pace_host.h")),
+    _hip_lib("ldspath", "ldspath", ("ldspath.hip",), ("ldspath.h", "ldspath_host.h")),
+)
+_CANARY, _HOSTLINK, _PACE, _LDSPATH = HIP_LIBS
+CANARY_SOURCES, CANARY_LIB = _CANARY["sources"], _CANARY["lib"]
+HOSTLINK_SOURCES, HOSTLINK_HEADERS, HOSTLINK_LIB = _HOSTLINK["sources"], _HOSTLINK["headers"], _HOSTLINK["lib"]
+PACE_SOURCES, PACE_HEADERS, PACE_LIB = _PACE["sources"], _PACE["headers"], _PACE["lib"]
+LDSPATH_SOURCES, LDSPATH_HEADERS, LDSPATH_LIB = _LDSPATH["sources"], _LDSPATH["headers"], _LDSPATH["lib"]
+HOSTLINK_DIR, PACE_DIR, LDSPATH_DIR = (os.path.dirname(lib) for lib in (HOSTLINK_LIB, PACE_LIB, LDSPATH_LIB))
 
 
 def native_ext_path() -> str:
@@ -331,73 +339,48 @@ def hipcc_path() -> str | None:
     return p if os.path.exists(p) else shutil.which("hipcc")
 
 
-def build_canary(force: bool = False, verbose: bool = True) -> str:
-    """hipcc the CDNA4 health-canary kernel library for gfx950 only."""
+def _build_hip_lib(name: str, lib: str, sources, headers, force: bool = False, verbose: bool = True) -> str:
+    """hipcc one library of ``HIP_LIBS`` for gfx950 only."""
     hipcc = hipcc_path()
     if hipcc is None:
         raise RuntimeError("hipcc not found under %s/bin" % ROCM)
-    if force or _stale(CANARY_LIB, CANARY_SOURCES + CANARY_HEADERS):
-        tmp = CANARY_LIB + ".tmp"
+    if force or _stale(lib, sources + headers):
+        tmp = lib + ".tmp"
         _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
-              "-Wall", "-o", tmp] + CANARY_SOURCES, "hipcc canary")
-        os.replace(tmp, CANARY_LIB)
+              "-Wall", "-o", tmp] + sources, "hipcc " + name)
+        os.replace(tmp, lib)
         if verbose:
-            print("built", os.path.relpath(CANARY_LIB, ROOT))
-    return CANARY_LIB
+            print("built", os.path.relpath(lib, ROOT))
+    return lib
+
+
+def build_canary(force: bool = False, verbose: bool = True) -> str:
+    """hipcc the CDNA4 health-canary kernel library for gfx950 only."""
+    return _build_hip_lib(force=force, verbose=verbose, **_CANARY)
 
 
 def build_hostlink(force: bool = False, verbose: bool = True) -> str:
-    """hipcc the host-link check (``ops/hostlink/``) for gfx950 only, as ``build_canary`` does."""
-    hipcc = hipcc_path()
-    if hipcc is None:
-        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
-    if force or _stale(HOSTLINK_LIB, HOSTLINK_SOURCES + HOSTLINK_HEADERS):
-        tmp = HOSTLINK_LIB + ".tmp"
-        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
-              "-Wall", "-o", tmp] + HOSTLINK_SOURCES, "hipcc hostlink")
-        os.replace(tmp, HOSTLINK_LIB)
-        if verbose:
-            print("built", os.path.relpath(HOSTLINK_LIB, ROOT))
-    return HOSTLINK_LIB
+    return _build_hip_lib(force=force, verbose=verbose, **_HOSTLINK)
 
 
 def build_pace(force: bool = False, verbose: bool = True) -> str:
-    """hipcc the pace check (``ops/pace/``) for gfx950 only, as ``build_canary`` does."""
-    hipcc = hipcc_path()
-    if hipcc is None:
-        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
-    if force or _stale(PACE_LIB, PACE_SOURCES + PACE_HEADERS):
-        tmp = PACE_LIB + ".tmp"
-        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
-              "-Wall", "-o", tmp] + PACE_SOURCES, "hipcc pace")
-        os.replace(tmp, PACE_LIB)
-        if verbose:
-            print("built", os.path.relpath(PACE_LIB, ROOT))
-    return PACE_LIB
+    return _build_hip_lib(force=force, verbose=verbose, **_PACE)
 
 
 def build_ldspath(force: bool = False, verbose: bool = True) -> str:
-    """hipcc the LDS-path check (``ops/ldspath/``) for gfx950 only, as ``build_canary`` does."""
-    hipcc = hipcc_path()
-    if hipcc is None:
-        raise RuntimeError("hipcc not found under %s/bin" % ROCM)
-    if force or _stale(LDSPATH_LIB, LDSPATH_SOURCES + LDSPATH_HEADERS):
-        tmp = LDSPATH_LIB + ".tmp"
-        _run([hipcc, "--offload-arch=" + OFFLOAD_ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
-              "-Wall", "-o", tmp] + LDSPATH_SOURCES, "hipcc ldspath")
-        os.replace(tmp, LDSPATH_LIB)
-        if verbose:
-            print("built", os.path.relpath(LDSPATH_LIB, ROOT))
-    return LDSPATH_LIB
+    return _build_hip_lib(force=force, verbose=verbose, **_LDSPATH)
+
+
+def build_canaries(force: bool = False) -> None:
+    """Every library of ``HIP_LIBS``."""
+    for row in HIP_LIBS:
+        _build_hip_lib(force=force, **row)
 
 
 def build_all(force: bool = False) -> None:
     build_native(force=force)
     build_bench(force=force)
-    build_canary(force=force)
-    build_hostlink(force=force)
-    build_pace(force=force)
-    build_ldspath(force=force)
+    build_canaries(force=force)
 
 
 def main(argv=None) -> int:
@@ -433,10 +416,7 @@ def main(argv=None) -> int:
     build_native(force=args.force)
     build_bench(force=args.force)
     if not args.no_canary:
-        build_canary(force=args.force)
-        build_hostlink(force=args.force)
-        build_pace(force=args.force)
-        build_ldspath(force=args.force)
+        build_canaries(force=args.force)
     return 0
 
 

@@ -27,10 +27,14 @@ from __future__ import annotations
 
 import argparse
 import ctypes
+import importlib
 import json
 import os
 import subprocess
 import sys
+from typing import NamedTuple
+
+from ._sites import SITE_SLOTS, UNWRITTEN, decode_site, format_site, load_library  # noqa: F401
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libamdgpu_canary.so")
 
@@ -53,7 +57,6 @@ class CanaryResult(ctypes.Structure):
                 ("xcd_pairs_unreached", ctypes.c_int)]
 
 
-SITE_SLOTS = 1 << 14
 SITE_CHECKS = ("mfma", "lowp", "valu")
 
 
@@ -100,14 +103,62 @@ class FabricResult(ctypes.Structure):
 
 
 CU_INJECT = ("vgpr", "agpr", "l1")
-# the rates the host-link check (ops/hostlink.py) merges into run()'s result
-HOST_LINK_RATES = ("kernel_read_gbps", "kernel_write_gbps", "copy_h2d_gbps", "copy_d2h_gbps")
-# what the LDS-path check (ops/ldspath.py) merges into run()'s result: (key there, key of ldspath_check)
-LDS_PATH_KEYS = (("ldspath_errors", "ldspath_errors"), ("lds_width_errors", "lds_errors"), ("lds_dma_errors", "dma_errors"),
-                 ("lds_atomic_errors", "lds_atomic_errors"), ("lane_errors", "lane_errors"), ("tr_errors", "tr_errors"),
-                 ("ldspath_ms", "ms"), ("ldspath_bad_sites", "bad_sites"))
-# what the pace check (ops/pace.py) merges into run()'s result under the same name
-PACE_KEYS = ("pace_errors", "clock_mhz_min", "clock_mhz_max", "clock_fraction", "xcd_pace_ratio", "xcd_mem_ratio")
+
+
+class OptionalCheck(NamedTuple):
+    """An opt-in check: a library and a Python face of its own, merged into ``run`` when asked for."""
+    keyword: str   # of run() and run_isolated()
+    stem: str      # "--<stem>": only this check; "--with-<stem>": the full run with it merged in
+    module: str    # its Python face in ops/, imported when it runs
+    function: str  # called as function(device, *args)
+    args: tuple    # (keyword of run(), default, key of health.*) of each further argument; "--<keyword>" on the command line
+    title: str     # "the pace check", for the help texts
+    detail: str    # what it covers, for the help text of "--<stem>"
+    keys: tuple    # (key in run()'s result, key of the check's result or a callable on it), in the order merged
+    errors: tuple  # (label, key) pairs it adds to amdgpu_canary_errors
+    switch: str    # the health.* option that turns it on
+
+
+# In the order run() merges them.  run_isolated's flags, main's arguments and the metric labels go in the
+# order the checks were added, which is the reverse.
+OPTIONAL_CHECKS = (
+    # lds_errors is already lds_march's count, so the width passes' is lds_width_errors
+    OptionalCheck("lds_path", "lds-path", "ldspath", "ldspath_check", (),
+                  "the LDS-path check", "LDS widths, atomics, lane swaps and the transposed read, per site",
+                  (("ldspath_errors", "ldspath_errors"), ("lds_width_errors", "lds_errors"), ("lds_dma_errors", "dma_errors"),
+                   ("lds_atomic_errors", "lds_atomic_errors"), ("lane_errors", "lane_errors"), ("tr_errors", "tr_errors"),
+                   ("ldspath_ms", "ms"), ("ldspath_bad_sites", "bad_sites")),
+                  (("lds_width", "lds_width_errors"), ("lds_dma", "lds_dma_errors"), ("lds_atomic", "lds_atomic_errors"),
+                   ("lane", "lane_errors"), ("lds_tr", "tr_errors")),
+                  "canaryLdsPath"),
+    # wrong results fail the run; slowness is carried as figures and pace_note for the caller's floors
+    OptionalCheck("pace", "pace", "pace", "pace_check", (),
+                  "the pace check", "in-kernel clock and rate per XCD, CU and SIMD",
+                  (("pace_errors", "pace_errors"), ("clock_mhz_min", "clock_mhz_min"), ("clock_mhz_max", "clock_mhz_max"),
+                   ("clock_fraction", "clock_fraction"), ("xcd_pace_ratio", "xcd_pace_ratio"),
+                   ("xcd_mem_ratio", "xcd_mem_ratio"), ("pace_slow_sites", "slow_sites"), ("pace_slow_xccs", "slow_xccs"),
+                   ("pace_ms", "ms"), ("pace_note", "note")),
+                  (("pace", "pace_errors"),),
+                  "canaryPace"),
+    OptionalCheck("host_link", "host-link", "hostlink", "host_link_check",
+                  (("host_link_bytes", 64 << 20, "canaryHostLinkBytes"),),
+                  "the host-link check", "PCIe reads, writes, copies and system atomics",
+                  (("host_read_errors", "read_errors"), ("host_write_errors", "write_errors"),
+                   ("host_copy_errors", lambda hl: hl["h2d_errors"] + hl["d2h_errors"]),
+                   ("host_atomic_errors", "atomic_errors"), ("kernel_read_gbps", "kernel_read_gbps"),
+                   ("kernel_write_gbps", "kernel_write_gbps"), ("copy_h2d_gbps", "copy_h2d_gbps"),
+                   ("copy_d2h_gbps", "copy_d2h_gbps"), ("host_ms", "ms")),
+                  (("host_read", "host_read_errors"), ("host_write", "host_write_errors"),
+                   ("host_copy", "host_copy_errors"), ("host_atomic", "host_atomic_errors")),
+                  "canaryHostLink"),
+)
+_LDS_PATH, _PACE, _HOST_LINK = OPTIONAL_CHECKS
+# what the LDS-path check merges into run()'s result: (key there, key of ldspath_check)
+LDS_PATH_KEYS = _LDS_PATH.keys
+# what the pace check merges into run()'s result under the same name
+PACE_KEYS = tuple(key for key, theirs in _PACE.keys if key == theirs)
+# the rates the host-link check merges into run()'s result
+HOST_LINK_RATES = tuple(key for key, _ in _HOST_LINK.keys if key.endswith("_gbps"))
 
 
 class CuSlot(ctypes.Structure):
@@ -126,98 +177,79 @@ class CuResult(ctypes.Structure):
                 ("l1_ms", ctypes.c_double)]
 
 
-def decode_site(packed: int) -> dict:
-    """Fields of a packed site: simd bits 1:0, cu 5:2, sh 6, se 9:7, xcc 13:10 (the layout
-    ``site_id()`` in ``ops/sites.hip`` builds from HW_REG_HW_ID and HW_REG_XCC_ID)."""
-    p = int(packed)
-    return {"xcc": (p >> 10) & 0xF, "se": (p >> 7) & 0x7, "sh": (p >> 6) & 0x1, "cu": (p >> 2) & 0xF, "simd": p & 0x3}
-
-
-def format_site(packed: int) -> str:
-    """``xcc3/se1/sh0/cu7/simd2``: XCD, shader engine, shader array, CU within it, SIMD."""
-    return "xcc%(xcc)d/se%(se)d/sh%(sh)d/cu%(cu)d/simd%(simd)d" % decode_site(packed)
-
-
-_lib = None
+def _declare(lib) -> None:
+    lib.amdgpu_canary_run.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
+                                      ctypes.POINTER(CanaryResult)]
+    lib.amdgpu_canary_run.restype = ctypes.c_int
+    lib.amdgpu_canary_device_count.restype = ctypes.c_int
+    lib.amdgpu_canary_mfma_gemm.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                            ctypes.c_int]
+    lib.amdgpu_canary_mfma_gemm.restype = ctypes.c_int
+    lib.amdgpu_canary_detects_corruption.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int]
+    lib.amdgpu_canary_detects_corruption.restype = ctypes.c_longlong
+    lib.amdgpu_canary_mfma_detects.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.amdgpu_canary_mfma_detects.restype = ctypes.c_longlong
+    lib.amdgpu_canary_hbm_sweep.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong)]
+    lib.amdgpu_canary_hbm_sweep.restype = ctypes.c_int
+    lib.amdgpu_canary_gemm.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
+                                       ctypes.c_int]
+    lib.amdgpu_canary_gemm.restype = ctypes.c_int
+    lib.amdgpu_canary_gemm_rate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
+                                            ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_canary_gemm_rate.restype = ctypes.c_int
+    lib.amdgpu_canary_abft.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                       ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
+                                       ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_canary_abft.restype = ctypes.c_int
+    lib.amdgpu_canary_gemm_tile_map.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_int]
+    lib.amdgpu_canary_gemm_tile_map.restype = ctypes.c_int
+    lib.amdgpu_canary_lowp_check.argtypes = [ctypes.c_int] * 5
+    lib.amdgpu_canary_lowp_check.restype = ctypes.c_longlong
+    lib.amdgpu_canary_lowp_rate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                            ctypes.POINTER(ctypes.c_double)]
+    lib.amdgpu_canary_lowp_rate.restype = ctypes.c_int
+    lib.amdgpu_canary_lds_check.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
+    lib.amdgpu_canary_lds_check.restype = ctypes.c_longlong
+    lib.amdgpu_canary_lowp_gemm.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
+        [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_canary_lowp_gemm.restype = ctypes.c_int
+    lib.amdgpu_canary_sites.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(SiteSlot),
+                                                             ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
+                                                             ctypes.POINTER(SitesResult), ctypes.c_char_p,
+                                                             ctypes.c_int]
+    lib.amdgpu_canary_sites.restype = ctypes.c_int
+    lib.amdgpu_canary_fabric.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(XccSlot), ctypes.POINTER(PairSlot),
+                                                              ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
+                                                              ctypes.POINTER(FabricResult), ctypes.c_char_p,
+                                                              ctypes.c_int]
+    lib.amdgpu_canary_fabric.restype = ctypes.c_int
+    lib.amdgpu_canary_fabric_describe.argtypes = [ctypes.POINTER(FabricResult), ctypes.POINTER(XccSlot),
+                                                  ctypes.POINTER(PairSlot), ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_canary_fabric_describe.restype = ctypes.c_int
+    lib.amdgpu_canary_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
+    lib.amdgpu_canary_atomic_expected.restype = ctypes.c_int
+    lib.amdgpu_canary_cu.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(CuSlot), ctypes.POINTER(ctypes.c_uint),
+                                                          ctypes.c_int, ctypes.POINTER(CuResult),
+                                                          ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_canary_cu.restype = ctypes.c_int
+    lib.amdgpu_canary_cu_describe.argtypes = [ctypes.POINTER(CuResult), ctypes.POINTER(CuSlot), ctypes.c_char_p,
+                                              ctypes.c_int]
+    lib.amdgpu_canary_cu_describe.restype = ctypes.c_int
+    lib.amdgpu_canary_cu_regs.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
+    lib.amdgpu_canary_cu_regs.restype = None
+    lib.amdgpu_canary_cu_sizeof.argtypes = [ctypes.c_int]
+    lib.amdgpu_canary_cu_sizeof.restype = ctypes.c_int
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            from .. import _build
-            _build.build_canary(verbose=False)
-        lib = ctypes.CDLL(LIB_PATH)
-        lib.amdgpu_canary_run.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
-                                          ctypes.POINTER(CanaryResult)]
-        lib.amdgpu_canary_run.restype = ctypes.c_int
-        lib.amdgpu_canary_device_count.restype = ctypes.c_int
-        lib.amdgpu_canary_mfma_gemm.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
-                                                ctypes.c_int]
-        lib.amdgpu_canary_mfma_gemm.restype = ctypes.c_int
-        lib.amdgpu_canary_detects_corruption.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int]
-        lib.amdgpu_canary_detects_corruption.restype = ctypes.c_longlong
-        lib.amdgpu_canary_mfma_detects.argtypes = [ctypes.c_int, ctypes.c_int]
-        lib.amdgpu_canary_mfma_detects.restype = ctypes.c_longlong
-        lib.amdgpu_canary_hbm_sweep.argtypes = [ctypes.c_int, ctypes.c_ulonglong, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                                ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_ulonglong)]
-        lib.amdgpu_canary_hbm_sweep.restype = ctypes.c_int
-        lib.amdgpu_canary_gemm.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_char_p,
-                                           ctypes.c_int]
-        lib.amdgpu_canary_gemm.restype = ctypes.c_int
-        lib.amdgpu_canary_gemm_rate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_double),
-                                                ctypes.POINTER(ctypes.c_ulonglong), ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_canary_gemm_rate.restype = ctypes.c_int
-        lib.amdgpu_canary_abft.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                           ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                           ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_ulonglong),
-                                           ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_canary_abft.restype = ctypes.c_int
-        lib.amdgpu_canary_gemm_tile_map.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                    ctypes.c_void_p, ctypes.c_int]
-        lib.amdgpu_canary_gemm_tile_map.restype = ctypes.c_int
-        lib.amdgpu_canary_lowp_check.argtypes = [ctypes.c_int] * 5
-        lib.amdgpu_canary_lowp_check.restype = ctypes.c_longlong
-        lib.amdgpu_canary_lowp_rate.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                ctypes.POINTER(ctypes.c_double)]
-        lib.amdgpu_canary_lowp_rate.restype = ctypes.c_int
-        lib.amdgpu_canary_lds_check.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_ulonglong)]
-        lib.amdgpu_canary_lds_check.restype = ctypes.c_longlong
-        lib.amdgpu_canary_lowp_gemm.argtypes = [ctypes.c_int, ctypes.c_int] + [ctypes.c_void_p] * 5 + \
-            [ctypes.c_int] * 3 + [ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_canary_lowp_gemm.restype = ctypes.c_int
-        lib.amdgpu_canary_sites.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(SiteSlot),
-                                                                 ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
-                                                                 ctypes.POINTER(SitesResult), ctypes.c_char_p,
-                                                                 ctypes.c_int]
-        lib.amdgpu_canary_sites.restype = ctypes.c_int
-        lib.amdgpu_canary_fabric.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(XccSlot), ctypes.POINTER(PairSlot),
-                                                                  ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
-                                                                  ctypes.POINTER(FabricResult), ctypes.c_char_p,
-                                                                  ctypes.c_int]
-        lib.amdgpu_canary_fabric.restype = ctypes.c_int
-        lib.amdgpu_canary_fabric_describe.argtypes = [ctypes.POINTER(FabricResult), ctypes.POINTER(XccSlot),
-                                                      ctypes.POINTER(PairSlot), ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_canary_fabric_describe.restype = ctypes.c_int
-        lib.amdgpu_canary_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]
-        lib.amdgpu_canary_atomic_expected.restype = ctypes.c_int
-        lib.amdgpu_canary_cu.argtypes = [ctypes.c_int] * 7 + [ctypes.POINTER(CuSlot), ctypes.POINTER(ctypes.c_uint),
-                                                              ctypes.c_int, ctypes.POINTER(CuResult),
-                                                              ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_canary_cu.restype = ctypes.c_int
-        lib.amdgpu_canary_cu_describe.argtypes = [ctypes.POINTER(CuResult), ctypes.POINTER(CuSlot), ctypes.c_char_p,
-                                                  ctypes.c_int]
-        lib.amdgpu_canary_cu_describe.restype = ctypes.c_int
-        lib.amdgpu_canary_cu_regs.argtypes = [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-        lib.amdgpu_canary_cu_regs.restype = None
-        lib.amdgpu_canary_cu_sizeof.argtypes = [ctypes.c_int]
-        lib.amdgpu_canary_cu_sizeof.restype = ctypes.c_int
-        _lib = lib
-    return _lib
+    return load_library(LIB_PATH, "build_canary", _declare)
 
 
 def device_count() -> int:
@@ -250,73 +282,31 @@ def run(device: int = 0, hbm_bytes: int = 1 << 30, passes: int = 3, mfma_iters: 
     if out["reg_errors"] or out["l1_errors"]:
         out["ok"] = False
         out["error"] = out["error"] or cu["error"]
-    if lds_path:
-        _merge_lds_path(out, device)
-    if pace:
-        _merge_pace(out, device)
-    if host_link:
-        _merge_host_link(out, device, host_link_bytes)
+    asked = {"lds_path": lds_path, "pace": pace, "host_link": host_link, "host_link_bytes": host_link_bytes}
+    for check in OPTIONAL_CHECKS:
+        if asked[check.keyword]:
+            _merge(out, check, device, *(asked[arg] for arg, _, _ in check.args))
     return out
 
 
-def _merge_lds_path(out: dict, device: int) -> None:
-    """The LDS-path check (``ops/ldspath.py``, a library of its own), same process and device.
-    ``lds_errors`` is already ``lds_march``'s count, so the width passes' is ``lds_width_errors``."""
-    from . import ldspath
+def _function(check: OptionalCheck):
+    return getattr(importlib.import_module("." + check.module, __package__), check.function)
+
+
+def _merge(out: dict, check: OptionalCheck, device: int, *args) -> None:
+    """One opt-in check (a library of its own), same process and device, merged into ``run``'s
+    verdict the way the CU memory check is."""
     try:
-        p = ldspath.ldspath_check(device)
+        p = _function(check)(device, *args)
     except (RuntimeError, OSError) as e:
         out["ok"] = False
         out["error"] = out["error"] or str(e)
         return
-    for key, theirs in LDS_PATH_KEYS:
-        out[key] = p[theirs]
+    for key, theirs in check.keys:
+        out[key] = theirs(p) if callable(theirs) else p[theirs]
     if not p["ok"]:
         out["ok"] = False
         out["error"] = out["error"] or p["error"]
-
-
-def _merge_pace(out: dict, device: int) -> None:
-    """The pace check (``ops/pace.py``, a library of its own), same process and device.  Wrong
-    results fail the run; slowness is carried as figures and ``pace_note`` for the caller's floors."""
-    from . import pace as pace_mod
-    try:
-        p = pace_mod.pace_check(device)
-    except (RuntimeError, OSError) as e:
-        out["ok"] = False
-        out["error"] = out["error"] or str(e)
-        return
-    for key in PACE_KEYS:
-        out[key] = p[key]
-    out["pace_slow_sites"] = p["slow_sites"]
-    out["pace_slow_xccs"] = p["slow_xccs"]
-    out["pace_ms"] = p["ms"]
-    out["pace_note"] = p["note"]
-    if not p["ok"]:
-        out["ok"] = False
-        out["error"] = out["error"] or p["error"]
-
-
-def _merge_host_link(out: dict, device: int, nbytes: int) -> None:
-    """The host-link check (``ops/hostlink.py``, a library of its own), same process and
-    device, merged into ``run``'s verdict the way the CU memory check is."""
-    from . import hostlink
-    try:
-        hl = hostlink.host_link_check(device, nbytes)
-    except (RuntimeError, OSError) as e:
-        out["ok"] = False
-        out["error"] = out["error"] or str(e)
-        return
-    out["host_read_errors"] = hl["read_errors"]
-    out["host_write_errors"] = hl["write_errors"]
-    out["host_copy_errors"] = hl["h2d_errors"] + hl["d2h_errors"]
-    out["host_atomic_errors"] = hl["atomic_errors"]
-    for rate in HOST_LINK_RATES:
-        out[rate] = hl[rate]
-    out["host_ms"] = hl["ms"]
-    if not hl["ok"]:
-        out["ok"] = False
-        out["error"] = out["error"] or hl["error"]
 
 
 def cu_check(device: int = 0, blocks: int = 0, reps: int = 2, l1_kb: int = 16, l1_reps: int = 4, inject=None,
@@ -360,8 +350,8 @@ def cu_check(device: int = 0, blocks: int = 0, reps: int = 2, l1_kb: int = 16, l
     out["sites"] = {format_site(p): {"waves": int(s.waves), "vgpr": int(s.bad_vgpr), "agpr": int(s.bad_agpr),
                                      "l1": int(s.bad_l1)}
                     for p, s in enumerate(table) if s.waves or s.bad_l1}
-    out["wave_sites"] = [format_site(p) for p in wave_sites[:n_waves] if p != 0xFFFFFFFF]  # unwritten: all-ones
-    out["l1_wave_sites"] = [format_site(p) for p in wave_sites[n_waves:] if p != 0xFFFFFFFF]
+    out["wave_sites"] = [format_site(p) for p in wave_sites[:n_waves] if p != UNWRITTEN]  # unwritten: all-ones
+    out["l1_wave_sites"] = [format_site(p) for p in wave_sites[n_waves:] if p != UNWRITTEN]
     lib.amdgpu_canary_cu_describe(ctypes.byref(r), table, err, 256)
     out["error"] = err.value.decode(errors="replace") if out["vgpr_errors"] or out["agpr_errors"] or \
         out["unlocated_errors"] or out["l1_errors"] else ""
@@ -395,7 +385,7 @@ def site_probe(device: int = 0, blocks: int = 0, ksteps: int = 4, inject=None, i
     out["ms"] = r.ms
     out["sites"] = {format_site(p): dict({"waves": int(s.waves)}, **{c: int(s.bad[i]) for i, c in enumerate(SITE_CHECKS)})
                     for p, s in enumerate(table) if s.waves}
-    out["wave_sites"] = [format_site(p) for p in wave_sites if p != 0xFFFFFFFF]  # unwritten entries stay all-ones
+    out["wave_sites"] = [format_site(p) for p in wave_sites if p != UNWRITTEN]  # unwritten entries stay all-ones
     return out
 
 
@@ -677,12 +667,12 @@ def run_isolated(device: int, hbm_bytes: int = 256 << 20, timeout: float = 120.0
     """``run`` in a child process (its own HIP runtime, gone when it exits)."""
     cmd = [sys.executable, "-m", "k8s_gpu_device_plugin_amd.ops.canary", "--device", str(device),
            "--bytes", str(hbm_bytes), "--passes", str(passes)]
-    if host_link:
-        cmd += ["--with-host-link", "--host-link-bytes", str(host_link_bytes)]
-    if pace:
-        cmd += ["--with-pace"]
-    if lds_path:
-        cmd += ["--with-lds-path"]
+    asked = {"lds_path": lds_path, "pace": pace, "host_link": host_link, "host_link_bytes": host_link_bytes}
+    for check in reversed(OPTIONAL_CHECKS):
+        if asked[check.keyword]:
+            cmd += ["--with-" + check.stem]
+            for arg, _, _ in check.args:
+                cmd += ["--" + arg.replace("_", "-"), str(asked[arg])]
     env = dict(os.environ)
     root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     env["PYTHONPATH"] = root + os.pathsep + env.get("PYTHONPATH", "")
@@ -718,32 +708,17 @@ def main(argv=None) -> int:
                     help="only the fabric check: L2 march, cross-XCD exchange, global atomics")
     ap.add_argument("--cu", action="store_true",
                     help="only the CU memory check: register-file march and L1 march, per site")
-    ap.add_argument("--host-link", action="store_true",
-                    help="only the host-link check: PCIe reads, writes, copies and system atomics")
-    ap.add_argument("--with-host-link", action="store_true", help="the full run, with the host-link check merged in")
-    ap.add_argument("--host-link-bytes", type=int, default=64 << 20)
-    ap.add_argument("--pace", action="store_true",
-                    help="only the pace check: in-kernel clock and rate per XCD, CU and SIMD")
-    ap.add_argument("--with-pace", action="store_true", help="the full run, with the pace check merged in")
-    ap.add_argument("--lds-path", action="store_true",
-                    help="only the LDS-path check: LDS widths, atomics, lane swaps and the transposed read, per site")
-    ap.add_argument("--with-lds-path", action="store_true", help="the full run, with the LDS-path check merged in")
+    for check in reversed(OPTIONAL_CHECKS):
+        ap.add_argument("--" + check.stem, action="store_true", help="only %s: %s" % (check.title, check.detail))
+        ap.add_argument("--with-" + check.stem, action="store_true", help="the full run, with %s merged in" % check.title)
+        for arg, default, _ in check.args:
+            ap.add_argument("--" + arg.replace("_", "-"), type=type(default), default=default)
     a = ap.parse_args(argv)
-    if a.lds_path:
-        from . import ldspath
-        res = ldspath.ldspath_check(a.device)
-        print(json.dumps(res))
-        return 0 if res["ok"] else 1
-    if a.pace:
-        from . import pace as pace_mod
-        res = pace_mod.pace_check(a.device)
-        print(json.dumps(res))
-        return 0 if res["ok"] else 1
-    if a.host_link:
-        from . import hostlink
-        res = hostlink.host_link_check(a.device, a.host_link_bytes)
-        print(json.dumps(res))
-        return 0 if res["ok"] else 1
+    for check in OPTIONAL_CHECKS:
+        if getattr(a, check.keyword):
+            res = _function(check)(a.device, *(getattr(a, arg) for arg, _, _ in check.args))
+            print(json.dumps(res))
+            return 0 if res["ok"] else 1
     if a.cu:
         res = cu_check(a.device)
         print(json.dumps(res))
@@ -762,11 +737,13 @@ def main(argv=None) -> int:
                         random_data=a.gemm_random)
         print(json.dumps(res))
         return 0 if not res["errors"] else 1
-    more = {"pace": True} if a.with_pace else {}  # passed only when asked for
-    if a.with_lds_path:
-        more["lds_path"] = True
-    res = run(a.device, a.bytes, a.passes, a.mfma_iters, host_link=a.with_host_link,
-              host_link_bytes=a.host_link_bytes, **more)
+    more = {}
+    for check in OPTIONAL_CHECKS:
+        on = getattr(a, "with_" + check.keyword)
+        if on or check.args:  # a check with arguments is always spelt out; the others are named only when asked for
+            more[check.keyword] = on
+            more.update({arg: getattr(a, arg) for arg, _, _ in check.args})
+    res = run(a.device, a.bytes, a.passes, a.mfma_iters, **more)
     print(json.dumps(res))
     return 0 if res["ok"] else 1
 

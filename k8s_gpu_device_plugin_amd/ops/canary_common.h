@@ -1,19 +1,21 @@
 // Shared by every gfx950 canary source (canary.hip, hbm.hip, gemm.hip, datapath.hip,
-// sites.hip, fabric.hip, cumem.hip).  Device side: the hash that derives exact small-integer
+// sites.hip, fabric.hip, cumem.hip) and, through canary_host.h, by the libraries of the
+// host-link, pace and LDS-path checks.  Device side: the hash that derives exact small-integer
 // operands, the MFMA register vector types and the 32x32 C/D row map, the bf16 / OCP
 // low-precision operand packing, the s_getreg immediates, site_id(), the wave and block error reductions.  And the C ABI,
 // declared here once: every result struct that canary.py mirrors with ctypes, with its size
 // pinned, and the prototype of every exported entry point that another source calls.  The
-// host-side helpers are in canary_host.h.
+// host-side helpers are in canary_host.h, the packed site and kMaxBlocks in site.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "site.h"
+
 namespace canary {
 
 constexpr int kWave = 64;
-constexpr int kMaxBlocks = 4096;  // grid cap of the located checks: the index of a wave of 4-wave workgroups < 2^14
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
@@ -137,9 +139,7 @@ __device__ __forceinline__ void block_add_errors(uint32_t bad, unsigned long lon
 }  // namespace canary
 
 // ---- site probe (sites.hip): where on the chip each exactness check ran ----------------
-// A site is (xcc, se, sh, cu, simd) packed into 14 bits:
-//   simd 1:0 | cu 5:2 | sh 6 | se 9:7 | xcc 13:10
-constexpr int kSiteSlots = 1 << 14;
+// A site is (xcc, se, sh, cu, simd) packed into 14 bits (site.h: kSiteSlots of them).
 
 namespace canary {
 

@@ -1,9 +1,10 @@
-// Host-side helpers of the gfx950 canary sources, header-only (every .hip file still compiles
-// on its own): the owners of device buffers and events, the sticky HIP status every entry
-// point reports through, the launch with the largest dynamic LDS allocation, the timing
-// sequence, the site text, and the prototypes of the functions one source calls in another
-// that are not part of the C ABI.  This is the only place that frees a device buffer or
-// destroys an event.
+// Host-side helpers of the gfx950 canary sources and of the host-link, pace and LDS-path
+// libraries, header-only (every .hip file still compiles on its own): the owners of device
+// buffers and events, the sticky HIP status every entry point reports through, the launch with
+// the largest dynamic LDS allocation, the timing sequence, and the prototypes of the functions
+// one source calls in another that are not part of the C ABI.  The site text, the coverage walk
+// and the launch plan come with canary_common.h from site.h.  This is the only place
+// that frees a device buffer or destroys an event.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -159,14 +160,6 @@ size_t launch_with_max_lds(Kernel kernel, const hipDeviceProp_t& prop, dim3 grid
     if (hipGetLastError() == hipSuccess) return bytes;
   }
   return 0;
-}
-
-// "xcc3/se1/sh0/cu7/simd2" of a packed site (canary_common.h), "xcc3/se1/sh0/cu7" without simd
-inline int format_site(unsigned int site, bool simd, char* buf, int len) {
-  int n = std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
-                        (site >> 2) & 0xFu);
-  if (simd && n > 0 && n < len) n += std::snprintf(buf + n, len - n, "/simd%u", site & 3u);
-  return n;
 }
 
 // hbm.hip: the warm-up write, then `passes` timed write + verify pairs over the n 16-byte

@@ -214,27 +214,18 @@ __global__ void __launch_bounds__(256) l1_march(const u32x4* buf, int slice_word
 // Fills the located totals and the coverage counts of `r` from host copies of the tables.
 void summarize(const amdgpu_canary_cu_slot* t, const unsigned int* cu_waves, amdgpu_canary_cu_result* r) {
   r->vgpr_errors = r->agpr_errors = r->l1_errors = r->waves = 0;
-  r->cus_reached = r->simds_reached = r->l1_cus_reached = r->n_bad = 0;
-  for (int cu = 0; cu < kSiteSlots / 4; ++cu) {
-    bool any = false;
-    for (int simd = 0; simd < 4; ++simd) {
-      const amdgpu_canary_cu_slot& s = t[cu * 4 + simd];
-      if (s.waves) {
-        any = true;
-        ++r->simds_reached;
-        r->waves += s.waves;
-      }
-      r->vgpr_errors += s.bad_vgpr;
-      r->agpr_errors += s.bad_agpr;
-      r->l1_errors += s.bad_l1;
-      if (s.bad_vgpr | s.bad_agpr | s.bad_l1) {
-        if (r->n_bad < 16) r->bad_sites[r->n_bad] = static_cast<unsigned int>(cu * 4 + simd);
-        ++r->n_bad;
-      }
-    }
-    r->cus_reached += any;
-    r->l1_cus_reached += cu_waves[cu] > 0;
+  r->l1_cus_reached = 0;
+  for (int i = 0; i < kSiteSlots; ++i) {
+    const amdgpu_canary_cu_slot& s = t[i];
+    r->waves += s.waves;
+    r->vgpr_errors += s.bad_vgpr;
+    r->agpr_errors += s.bad_agpr;
+    r->l1_errors += s.bad_l1;  // l1_march may add these at a site no reg_march wave stayed on: bad without a wave
   }
+  for (int cu = 0; cu < kSiteSlots / 4; ++cu) r->l1_cus_reached += cu_waves[cu] > 0;
+  store_coverage(site_coverage([&](int i) { return t[i].waves != 0; },
+                               [&](int i) { return (t[i].bad_vgpr | t[i].bad_agpr | t[i].bad_l1) != 0; }),
+                 r);
 }
 
 }  // namespace
@@ -327,14 +318,11 @@ int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, i
   DeviceBuffer<u32x4> d_buf;
   Events<3> ev;
   const int slice_words = l1_kb * 64;  // 16-B words; a multiple of 256
-  int grid = 0;
+  LaunchPlan plan = {0, 0};
   CANARY_HIP(st, hipSetDevice(device));
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
-  if (st.ok()) {
-    grid = blocks == 0 ? 2 * prop.multiProcessorCount : blocks;
-    if (grid > kMaxBlocks) grid = kMaxBlocks;
-    if (grid < 1) grid = 1;
-  }
+  if (st.ok()) plan = launch_plan(blocks, prop.multiProcessorCount, 2, true);
+  const int grid = plan.grid;
   CANARY_HIP(st, d_buf.alloc(static_cast<size_t>(grid) * slice_words * sizeof(u32x4)));
   CANARY_HIP(st, d_table.alloc(sizeof(amdgpu_canary_cu_slot) * kSiteSlots));
   CANARY_HIP(st, d_table.zero());
@@ -349,8 +337,7 @@ int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, i
   CANARY_HIP(st, ev.create());
   if (st.ok()) {
     out->cus_expected = prop.multiProcessorCount;
-    const int max_launches = blocks == 0 ? 4 : 1;
-    for (int l = 0; l < max_launches; ++l) {
+    for (int l = 0; l < plan.max_launches; ++l) {
       float ms[2] = {0, 0};  // reg_march; l1_fill and l1_march
       const int inj = l == 0 ? inject_kind : -1;
       time_stages(st, ev, ms, [&](int k) {
@@ -383,9 +370,7 @@ int amdgpu_canary_cu(int device, int blocks, int reps, int l1_kb, int l1_reps, i
       out->l1_ms += ms[1];
       out->launches = l + 1;
       summarize(table, cu_waves.data(), out);
-      if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected &&
-          out->l1_cus_reached >= out->cus_expected)
-        break;
+      if (covered(*out, out->cus_expected) && out->l1_cus_reached >= out->cus_expected) break;
     }
   }
   CANARY_HIP(st, d_counters.download(h_counters));

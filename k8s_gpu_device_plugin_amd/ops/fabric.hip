@@ -543,9 +543,7 @@ int amdgpu_canary_fabric(int device, int blocks, int slice_kb, int reps, int inj
   CANARY_HIP(st, hipSetDevice(device));
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
   if (st.ok()) {
-    grid = blocks > 0 ? blocks : prop.multiProcessorCount;
-    if (grid > kMaxBlocks) grid = kMaxBlocks;
-    if (grid < 1) grid = 1;
+    grid = launch_plan(blocks, prop.multiProcessorCount, 1).grid;
     out->blocks = grid;
     out->slice_kb = slice_kb;
     h_state.assign(kSliceXccOff + sizeof(unsigned int) * grid, 0);

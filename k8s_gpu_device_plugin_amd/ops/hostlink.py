@@ -13,9 +13,10 @@ from __future__ import annotations
 import ctypes
 import os
 
+from ._sites import XCCS, load_library
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostlink", "libamdgpu_hostlink.so")
 
-XCCS = 16
 # the system-scope atomic forms, in the order of ops/hostlink/hostlink_host.h
 ATOMIC_OPS = ("u32_add", "u64_add", "ticket", "cas_inc", "swap")
 INJECT = ("read", "write", "h2d", "d2h", "atomic")
@@ -49,42 +50,35 @@ class HostLinkResult(ctypes.Structure):
                 ("host_cpu_ms", ctypes.c_double)]
 
 
-_lib = None
+def _declare(lib) -> None:
+    lib.amdgpu_hostlink_run.argtypes = [ctypes.c_int, ctypes.c_ulonglong] + [ctypes.c_int] * 8 + \
+        [ctypes.POINTER(XccSlot), ctypes.POINTER(ctypes.c_uint), ctypes.c_int, ctypes.POINTER(HostLinkResult),
+         ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_hostlink_run.restype = ctypes.c_int
+    lib.amdgpu_hostlink_describe.argtypes = [ctypes.POINTER(HostLinkResult), ctypes.POINTER(XccSlot),
+                                             ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_hostlink_describe.restype = ctypes.c_int
+    lib.amdgpu_hostlink_sizeof.argtypes = [ctypes.c_int]
+    lib.amdgpu_hostlink_sizeof.restype = ctypes.c_int
+    lib.amdgpu_hostlink_tile_words.argtypes = [ctypes.c_int]
+    lib.amdgpu_hostlink_tile_words.restype = ctypes.c_int
+    lib.amdgpu_hostlink_pattern.argtypes = [ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_void_p]
+    lib.amdgpu_hostlink_pattern.restype = ctypes.c_int
+    lib.amdgpu_hostlink_verify.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_uint,
+                                           ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_longlong)]
+    lib.amdgpu_hostlink_verify.restype = ctypes.c_int
+    lib.amdgpu_hostlink_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                    ctypes.c_int]
+    lib.amdgpu_hostlink_atomic_expected.restype = ctypes.c_int
+    lib.amdgpu_hostlink_atomic_compare.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    lib.amdgpu_hostlink_atomic_compare.restype = ctypes.c_longlong
+    lib.amdgpu_hostlink_atomic_op_name.argtypes = [ctypes.c_int]
+    lib.amdgpu_hostlink_atomic_op_name.restype = ctypes.c_char_p
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            from .. import _build
-            _build.build_hostlink(verbose=False)
-        lib = ctypes.CDLL(LIB_PATH)
-        lib.amdgpu_hostlink_run.argtypes = [ctypes.c_int, ctypes.c_ulonglong] + [ctypes.c_int] * 8 + \
-            [ctypes.POINTER(XccSlot), ctypes.POINTER(ctypes.c_uint), ctypes.c_int, ctypes.POINTER(HostLinkResult),
-             ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_hostlink_run.restype = ctypes.c_int
-        lib.amdgpu_hostlink_describe.argtypes = [ctypes.POINTER(HostLinkResult), ctypes.POINTER(XccSlot),
-                                                 ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_hostlink_describe.restype = ctypes.c_int
-        lib.amdgpu_hostlink_sizeof.argtypes = [ctypes.c_int]
-        lib.amdgpu_hostlink_sizeof.restype = ctypes.c_int
-        lib.amdgpu_hostlink_tile_words.argtypes = [ctypes.c_int]
-        lib.amdgpu_hostlink_tile_words.restype = ctypes.c_int
-        lib.amdgpu_hostlink_pattern.argtypes = [ctypes.c_ulonglong, ctypes.c_ulonglong, ctypes.c_uint, ctypes.c_void_p]
-        lib.amdgpu_hostlink_pattern.restype = ctypes.c_int
-        lib.amdgpu_hostlink_verify.argtypes = [ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_uint,
-                                               ctypes.POINTER(ctypes.c_ulonglong), ctypes.POINTER(ctypes.c_longlong)]
-        lib.amdgpu_hostlink_verify.restype = ctypes.c_int
-        lib.amdgpu_hostlink_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                        ctypes.c_int]
-        lib.amdgpu_hostlink_atomic_expected.restype = ctypes.c_int
-        lib.amdgpu_hostlink_atomic_compare.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                                       ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-        lib.amdgpu_hostlink_atomic_compare.restype = ctypes.c_longlong
-        lib.amdgpu_hostlink_atomic_op_name.argtypes = [ctypes.c_int]
-        lib.amdgpu_hostlink_atomic_op_name.restype = ctypes.c_char_p
-        _lib = lib
-    return _lib
+    return load_library(LIB_PATH, "build_hostlink", _declare)
 
 
 def tile_words(unroll: int = 0) -> int:

@@ -1,6 +1,7 @@
 // C ABI of the host-link check (ops/hostlink/libamdgpu_hostlink.so), mirrored with ctypes in
 // ops/hostlink.py, and the owner of pinned host memory.  The library is built apart from
-// libamdgpu_canary.so and shares its header-only helpers (../canary_common.h, ../canary_host.h).
+// libamdgpu_canary.so and shares its header-only helpers (../canary_common.h, ../canary_host.h,
+// ../site.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -236,8 +236,6 @@ void flip_words(Word16* buf, uint64_t n, int count) {
   for (int f = 0; f < count; ++f) buf[hostlink::inject_word(n, count, f)].c[hostlink::kInjectComp] ^= 1u << hostlink::kInjectBit;
 }
 
-const char* plural(unsigned long long n) { return n == 1 ? "" : "s"; }
-
 }  // namespace
 
 extern "C" {
@@ -363,9 +361,7 @@ int amdgpu_hostlink_run(int device, unsigned long long bytes, int blocks, int re
   CANARY_HIP(st, hipSetDevice(device));
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
   if (st.ok()) {
-    grid = blocks > 0 ? blocks : prop.multiProcessorCount;
-    if (grid > kMaxBlocks) grid = kMaxBlocks;
-    if (grid < 1) grid = 1;
+    grid = launch_plan(blocks, prop.multiProcessorCount, 1).grid;
     out->blocks = grid;
     out->atomic_blocks = agrid;
     out->reps = reps;

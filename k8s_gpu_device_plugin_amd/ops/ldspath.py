@@ -13,13 +13,13 @@ from __future__ import annotations
 import ctypes
 import os
 
+from ._sites import SITE_SLOTS, UNWRITTEN, as_records, format_site, load_library, pack_site  # noqa: F401
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ldspath", "libamdgpu_ldspath.so")
 
-SITE_SLOTS = 1 << 14
 WAVES = 4  # per workgroup: records[block * 4 + wave]
 STAGES = ("widths", "atomic", "lane", "tr")
 SUBS = 48
-UNWRITTEN = 0xFFFFFFFF
 INJECT = ("lds", "subword", "dma", "atomic", "lane", "tr")
 SRC_ZERO = 128  # lane_map code of a lane that reads 0 (64 + l: the second value of lane l)
 ATOMIC_WORDS = 512
@@ -51,31 +51,24 @@ class LdsPathResult(ctypes.Structure):
         [(f, ctypes.c_int) for f in _TAIL]
 
 
-_lib = None
+def _declare(lib) -> None:
+    uint_p, int_p = ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)
+    lib.amdgpu_ldspath_run.argtypes = [ctypes.c_int] * 8 + [uint_p, ctypes.c_int, ctypes.POINTER(LdsPathResult),
+                                                            ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_ldspath_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int] * 4 + [ctypes.POINTER(LdsPathResult)]
+    lib.amdgpu_ldspath_lane_sources.argtypes = [ctypes.c_int, uint_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_ldspath_lane_map.argtypes = [ctypes.c_int, int_p]
+    lib.amdgpu_ldspath_tr_map.argtypes = [ctypes.c_int, int_p, int_p]
+    lib.amdgpu_ldspath_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, uint_p, ctypes.c_int]
+    lib.amdgpu_ldspath_describe.argtypes = [ctypes.POINTER(LdsPathResult), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_ldspath_sizeof.argtypes = [ctypes.c_int]
+    lib.amdgpu_ldspath_ops.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
+    for name in ("run", "reduce", "lane_sources", "lane_map", "tr_map", "atomic_expected", "describe", "sizeof", "ops"):
+        getattr(lib, "amdgpu_ldspath_" + name).restype = ctypes.c_int
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            from .. import _build
-            _build.build_ldspath(verbose=False)
-        lib = ctypes.CDLL(LIB_PATH)
-        uint_p, int_p = ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_int)
-        lib.amdgpu_ldspath_run.argtypes = [ctypes.c_int] * 8 + [uint_p, ctypes.c_int, ctypes.POINTER(LdsPathResult),
-                                                                ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_ldspath_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int] * 4 + [ctypes.POINTER(LdsPathResult)]
-        lib.amdgpu_ldspath_lane_sources.argtypes = [ctypes.c_int, uint_p, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_ldspath_lane_map.argtypes = [ctypes.c_int, int_p]
-        lib.amdgpu_ldspath_tr_map.argtypes = [ctypes.c_int, int_p, int_p]
-        lib.amdgpu_ldspath_atomic_expected.argtypes = [ctypes.c_int, ctypes.c_int, uint_p, ctypes.c_int]
-        lib.amdgpu_ldspath_describe.argtypes = [ctypes.POINTER(LdsPathResult), ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_ldspath_sizeof.argtypes = [ctypes.c_int]
-        lib.amdgpu_ldspath_ops.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]
-        for name in ("run", "reduce", "lane_sources", "lane_map", "tr_map", "atomic_expected", "describe", "sizeof", "ops"):
-            getattr(lib, "amdgpu_ldspath_" + name).restype = ctypes.c_int
-        _lib = lib
-    return _lib
+    return load_library(LIB_PATH, "build_ldspath", _declare)
 
 
 def _names(table: int) -> tuple:
@@ -101,18 +94,6 @@ def __getattr__(name):  # the tables are the library's: read on first use, so im
     if name in _TABLES:
         return _table(name)
     raise AttributeError(name)
-
-
-def format_site(packed: int, simd: bool = True) -> str:
-    """``xcc3/se1/sh0/cu7/simd2`` of a packed site (simd 1:0, cu 5:2, sh 6, se 9:7, xcc 13:10)."""
-    p = int(packed)
-    cu = "xcc%d/se%d/sh%d/cu%d" % ((p >> 10) & 0xF, (p >> 7) & 0x7, (p >> 6) & 0x1, (p >> 2) & 0xF)
-    return cu + "/simd%d" % (p & 0x3) if simd else cu
-
-
-def pack_site(xcc: int, se: int = 0, sh: int = 0, cu: int = 0, simd: int = 0) -> int:
-    """The packed form of a site, as ``site_id()`` in ``ops/canary_common.h`` builds it."""
-    return (int(xcc) & 0xF) << 10 | (int(se) & 0x7) << 7 | (int(sh) & 0x1) << 6 | (int(cu) & 0xF) << 2 | (int(simd) & 0x3)
 
 
 def _as_dict(lib, r) -> dict:
@@ -190,14 +171,7 @@ def reduce(widths=None, atomic=None, lane=None, tr=None) -> dict:
     """The check's host reduction on caller-supplied records of the four stages (numpy arrays of
     ``RECORD_DTYPE``, or rows for ``records()``), no GPU.  Returns what ``ldspath_check`` returns
     except the coverage target, the device times and ``wave_sites``."""
-    import numpy as np
-
-    def prepare(a):
-        if a is None:
-            return np.zeros(0, dtype=RECORD_DTYPE)
-        a = a if isinstance(a, np.ndarray) and a.dtype.names else records(a)
-        return np.ascontiguousarray(a, dtype=RECORD_DTYPE)
-    arrays = [prepare(a) for a in (widths, atomic, lane, tr)]
+    arrays = [as_records(a, RECORD_DTYPE, records) for a in (widths, atomic, lane, tr)]
     lib = load()
     r = LdsPathResult()
     args = []

@@ -1,7 +1,7 @@
 // C ABI of the LDS-path check (ops/ldspath/libamdgpu_ldspath.so), mirrored with ctypes in
 // ops/ldspath.py.  The library is built apart from libamdgpu_canary.so and shares its
-// header-only helpers (../canary_common.h, ../canary_host.h); the tables, the structs and the
-// reduction are in ldspath_host.h.
+// header-only helpers (../canary_common.h, ../canary_host.h, ../site.h); the tables, the
+// structs and the reduction are in ldspath_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

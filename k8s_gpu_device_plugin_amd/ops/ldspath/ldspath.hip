@@ -555,11 +555,8 @@ int amdgpu_ldspath_run(int device, int blocks, int reps, int steps, int rounds, 
   CANARY_HIP(st, hipSetDevice(device));
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
   if (!st.ok()) return st.report("ldspath check: ", err, err_len);
-  const bool automatic = blocks == 0;
-  int grid = automatic ? 2 * prop.multiProcessorCount : blocks;
-  if (grid > kMaxBlocks) grid = kMaxBlocks;
-  if (grid < 1) grid = 1;
-  const int max_launches = automatic ? 4 : 1;
+  const LaunchPlan plan = launch_plan(blocks, prop.multiProcessorCount, 2, true);
+  const int grid = plan.grid, max_launches = plan.max_launches;
   const size_t slots = static_cast<size_t>(grid) * kLdsWaves;
   out->cus_expected = prop.multiProcessorCount;
   out->blocks = grid;
@@ -642,7 +639,7 @@ int amdgpu_ldspath_run(int device, int blocks, int reps, int steps, int rounds, 
       std::snprintf(err, err_len, "ldspath check: a record holds a site out of range");
       return -1;
     }
-    if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected) break;
+    if (covered(*out, out->cus_expected)) break;
   }
   if (wave_site_len > 0) CANARY_HIP(st, d_wave_site.download(wave_site_out));
   return st.report("ldspath check: ", err, err_len);

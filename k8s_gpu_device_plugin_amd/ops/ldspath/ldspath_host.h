@@ -1,7 +1,8 @@
 // The LDS-path check's shared side: everything ldspath.hip's kernels and the host must agree
 // on, written once.  The patterns, the width-pass table, the lane-op table with its lane map,
 // the transposed-read address map, the atomics' operand functions and expected tables, the
-// record every wave leaves, the result, the reduction of the records and the texts.  No HIP
+// record every wave leaves, the result, the reduction of the records and the texts; the packed
+// site, its text and the coverage walk are ../site.h's.  No HIP
 // include: a plain C++17 compiler compiles it (tests/native/ldspath_selftest.cpp), and under
 // hipcc the functions marked LDSPATH_HD are compiled for the device too, so both sides run the
 // same code.
@@ -11,6 +12,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../site.h"
+
 #ifdef __HIPCC__
 #define LDSPATH_HD __host__ __device__ inline
 #else
@@ -19,11 +22,11 @@
 
 extern "C" {
 
-constexpr int kLdsSiteSlots = 1 << 14;  // packed sites: simd 1:0 | cu 5:2 | sh 6 | se 9:7 | xcc 13:10
+constexpr int kLdsSiteSlots = kSiteSlots;  // packed sites (site.h)
 constexpr int kLdsWaves = 4;            // waves per workgroup: records[block * 4 + wave]
 constexpr int kLdsStages = 4;           // 0 lds_widths, 1 lds_atomic, 2 lane_xchg, 3 lds_tr
 constexpr int kLdsSubs = 48;            // sub-checks a record counts: passes, forms, ops, or 1
-constexpr unsigned int kLdsUnwritten = 0xFFFFFFFFu;  // site_first of a slot no wave wrote; first_sub: nothing wrong
+constexpr unsigned int kLdsUnwritten = kSiteUnwritten;  // site_first of a slot no wave wrote; first_sub: nothing wrong
 
 struct amdgpu_ldspath_record {  // what one wave leaves per stage; 208 bytes
   unsigned int site_first;      // site_id() before the work
@@ -71,7 +74,13 @@ struct amdgpu_ldspath_result {
 
 namespace ldspath {
 
-constexpr int kMaxBlocks = 4096, kMaxReps = 64, kMaxSteps = 64, kMaxRounds = 64;
+using canary::format_site;
+using canary::kMaxBlocks;
+using canary::located;
+using canary::plural;
+using canary::records_valid;
+
+constexpr int kMaxReps = 64, kMaxSteps = 64, kMaxRounds = 64;
 constexpr int kThreads = 256;
 constexpr uint32_t kInjectBit = 1u << 9;
 constexpr int kInjectLane = 3;
@@ -372,26 +381,8 @@ LDSPATH_HD int tr_source(int l, int q, int r) {
 }
 
 // ---- records -> result ---------------------------------------------------------------------
-inline bool located(const amdgpu_ldspath_record& r) { return r.site_first == r.site_last; }
-
-inline int format_site(unsigned int site, bool simd, char* buf, int len) {
-  int n = std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
-                        (site >> 2) & 0xFu);
-  if (simd && n > 0 && n < len) n += std::snprintf(buf + n, len - n, "/simd%u", site & 3u);
-  return n;
-}
-
 inline int stage_subs(int stage) {
   return stage == 0 ? kNumWidthPasses : stage == 1 ? kAtomForms : stage == 2 ? kNumLaneOps : 1;
-}
-
-inline bool records_valid(const amdgpu_ldspath_record* r, int n) {
-  for (int i = 0; i < n; ++i) {
-    if (r[i].site_first == kLdsUnwritten) continue;
-    if (r[i].site_first >= static_cast<unsigned int>(kLdsSiteSlots) || r[i].site_last >= static_cast<unsigned int>(kLdsSiteSlots))
-      return false;
-  }
-  return true;
 }
 
 // recs[s] / n[s]: stage s's records in launch order (unwritten slots are skipped); any may be
@@ -463,26 +454,12 @@ inline bool reduce(const amdgpu_ldspath_record* const recs[kLdsStages], const in
   // wrong DMA words may be L2's or HBM's; beside wrong plain-store words they are the LDS's again and are not added
   r.ldspath_errors = r.lds_errors + (r.lds_errors == 0 ? r.dma_errors : 0) + r.lds_atomic_errors + r.lane_errors +
                      r.tr_errors + r.unlocated_errors;
-  for (int cu = 0; cu < kLdsSiteSlots / 4; ++cu) {
-    bool any = false;
-    for (int simd = 0; simd < 4; ++simd) {
-      const int site = cu * 4 + simd;
-      if (reached[site]) {
-        any = true;
-        ++r.simds_reached;
-      }
-      if (site_bad[site]) {
-        if (r.n_bad < 16) r.bad_sites[r.n_bad] = static_cast<unsigned int>(site);
-        ++r.n_bad;
-      }
-    }
-    r.cus_reached += any;
-  }
+  canary::store_coverage(canary::site_coverage([&](int site) { return reached[site] != 0; },
+                                               [&](int site) { return site_bad[site] != 0; }),
+                         &r);
   *out = r;
   return true;
 }
-
-inline const char* plural(unsigned long long n) { return n == 1 ? "" : "s"; }
 
 // "+1 more CU" / "+2 more sites", empty when there are no others
 inline void more_text(char* buf, int len, int others, const char* unit) {

@@ -12,12 +12,12 @@ from __future__ import annotations
 import ctypes
 import os
 
+from ._sites import SITE_SLOTS, UNWRITTEN, XCCS, as_records, format_site, load_library, pack_site  # noqa: F401
+from ._sites import xcc_names as _xcc_names
+
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "pace", "libamdgpu_pace.so")
 
-XCCS = 16
-SITE_SLOTS = 1 << 14
 WAVES = 4  # per workgroup: records[block * 4 + wave]
-UNWRITTEN = 0xFFFFFFFF
 INJECT = ("slow_xcc", "slow_waves", "result")
 # numpy mirror of amdgpu_pace_record: 32 bytes
 RECORD_DTYPE = [("site_first", "<u4"), ("site_last", "<u4"), ("cycles", "<u8"), ("ticks", "<u8"), ("work", "<u4"),
@@ -56,54 +56,32 @@ class PaceResult(ctypes.Structure):
         [(f, ctypes.c_uint) for f in _TAIL[:3]] + [(f, ctypes.c_int) for f in _TAIL[3:]]
 
 
-_lib = None
+def _declare(lib) -> None:
+    lib.amdgpu_pace_run.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] + [ctypes.c_int] * 4 + \
+        [ctypes.POINTER(SiteSlot), ctypes.POINTER(XccSlot), ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
+         ctypes.POINTER(PaceResult), ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_pace_run.restype = ctypes.c_int
+    lib.amdgpu_pace_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + \
+        [ctypes.c_double] * 3 + [ctypes.POINTER(SiteSlot), ctypes.POINTER(XccSlot), ctypes.POINTER(PaceResult)]
+    lib.amdgpu_pace_reduce.restype = ctypes.c_int
+    lib.amdgpu_pace_describe.argtypes = [ctypes.POINTER(PaceResult), ctypes.POINTER(XccSlot), ctypes.c_char_p,
+                                         ctypes.c_int]
+    lib.amdgpu_pace_describe.restype = ctypes.c_int
+    lib.amdgpu_pace_note.argtypes = [ctypes.POINTER(PaceResult), ctypes.POINTER(XccSlot), ctypes.POINTER(SiteSlot),
+                                     ctypes.c_char_p, ctypes.c_int]
+    lib.amdgpu_pace_note.restype = ctypes.c_int
+    lib.amdgpu_pace_sizeof.argtypes = [ctypes.c_int]
+    lib.amdgpu_pace_sizeof.restype = ctypes.c_int
+    lib.amdgpu_pace_default_iters.argtypes = []
+    lib.amdgpu_pace_default_iters.restype = ctypes.c_int
 
 
 def load():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            from .. import _build
-            _build.build_pace(verbose=False)
-        lib = ctypes.CDLL(LIB_PATH)
-        lib.amdgpu_pace_run.argtypes = [ctypes.c_int] * 4 + [ctypes.c_double] + [ctypes.c_int] * 4 + \
-            [ctypes.POINTER(SiteSlot), ctypes.POINTER(XccSlot), ctypes.POINTER(ctypes.c_uint), ctypes.c_int,
-             ctypes.POINTER(PaceResult), ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_pace_run.restype = ctypes.c_int
-        lib.amdgpu_pace_reduce.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + \
-            [ctypes.c_double] * 3 + [ctypes.POINTER(SiteSlot), ctypes.POINTER(XccSlot), ctypes.POINTER(PaceResult)]
-        lib.amdgpu_pace_reduce.restype = ctypes.c_int
-        lib.amdgpu_pace_describe.argtypes = [ctypes.POINTER(PaceResult), ctypes.POINTER(XccSlot), ctypes.c_char_p,
-                                             ctypes.c_int]
-        lib.amdgpu_pace_describe.restype = ctypes.c_int
-        lib.amdgpu_pace_note.argtypes = [ctypes.POINTER(PaceResult), ctypes.POINTER(XccSlot), ctypes.POINTER(SiteSlot),
-                                         ctypes.c_char_p, ctypes.c_int]
-        lib.amdgpu_pace_note.restype = ctypes.c_int
-        lib.amdgpu_pace_sizeof.argtypes = [ctypes.c_int]
-        lib.amdgpu_pace_sizeof.restype = ctypes.c_int
-        lib.amdgpu_pace_default_iters.argtypes = []
-        lib.amdgpu_pace_default_iters.restype = ctypes.c_int
-        _lib = lib
-    return _lib
-
-
-def format_site(packed: int) -> str:
-    """``xcc3/se1/sh0/cu7/simd2`` of a packed site (simd 1:0, cu 5:2, sh 6, se 9:7, xcc 13:10)."""
-    p = int(packed)
-    return "xcc%d/se%d/sh%d/cu%d/simd%d" % ((p >> 10) & 0xF, (p >> 7) & 0x7, (p >> 6) & 0x1, (p >> 2) & 0xF, p & 0x3)
-
-
-def pack_site(xcc: int, se: int = 0, sh: int = 0, cu: int = 0, simd: int = 0) -> int:
-    """The packed form of a site, as ``site_id()`` in ``ops/canary_common.h`` builds it."""
-    return (int(xcc) & 0xF) << 10 | (int(se) & 0x7) << 7 | (int(sh) & 0x1) << 6 | (int(cu) & 0xF) << 2 | (int(simd) & 0x3)
+    return load_library(LIB_PATH, "build_pace", _declare)
 
 
 def default_iters() -> int:
     return int(load().amdgpu_pace_default_iters())
-
-
-def _xcc_names(mask: int) -> list:
-    return ["xcc%d" % x for x in range(XCCS) if mask >> x & 1]
 
 
 def _as_dict(lib, r, sites, xccs) -> dict:
@@ -191,14 +169,7 @@ def reduce(mfma_records, tick_mhz: float, clock_max_mhz: float, slow_ratio: floa
     or rows for ``records()``), no GPU: ``mfma_records`` in launch order, ``mem_records`` (four
     per workgroup, wave 0 first) optional.  Returns what ``pace_check`` returns except the
     coverage target, the device times and ``wave_sites``."""
-    import numpy as np
-
-    def prepare(a):
-        if a is None:
-            return np.zeros(0, dtype=RECORD_DTYPE)
-        a = a if isinstance(a, np.ndarray) and a.dtype.names else records(a)
-        return np.ascontiguousarray(a, dtype=RECORD_DTYPE)
-    a, m = prepare(mfma_records), prepare(mem_records)
+    a, m = (as_records(x, RECORD_DTYPE, records) for x in (mfma_records, mem_records))
     lib = load()
     r = PaceResult()
     sites = (SiteSlot * SITE_SLOTS)()

@@ -1,6 +1,7 @@
 // C ABI of the pace check (ops/pace/libamdgpu_pace.so), mirrored with ctypes in ops/pace.py.
 // The library is built apart from libamdgpu_canary.so and shares its header-only helpers
-// (../canary_common.h, ../canary_host.h); the structs and the reduction are in pace_host.h.
+// (../canary_common.h, ../canary_host.h, ../site.h); the structs and the reduction are
+// in pace_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -282,20 +282,15 @@ int amdgpu_pace_run(int device, int blocks, int iters, int slice_kb, double slow
     return -1;
   }
   const double tick_mhz = wall_khz / 1000.0, clock_max_mhz = clock_khz > 0 ? clock_khz / 1000.0 : 0.0;
-  const bool automatic = blocks == 0;
-  int grid = automatic ? 2 * prop.multiProcessorCount : blocks;
-  if (grid > kMaxBlocks) grid = kMaxBlocks;
-  if (grid < 1) grid = 1;
-  int mem_grid = automatic ? prop.multiProcessorCount : blocks;
-  if (mem_grid > kMaxBlocks) mem_grid = kMaxBlocks;
-  if (mem_grid < 1) mem_grid = 1;
+  const LaunchPlan plan = launch_plan(blocks, prop.multiProcessorCount, 2, true);
+  const int grid = plan.grid, max_launches = plan.max_launches;
+  const int mem_grid = launch_plan(blocks, prop.multiProcessorCount, 1).grid;
   const int slice_words = slice_kb * 64;  // a multiple of 256
   const uint64_t mem_words = static_cast<uint64_t>(mem_grid) * static_cast<uint64_t>(slice_words);
   if (mem_words * 16u > pace::kMaxMemBytes) {
     bad_arguments(err, err_len, blocks, iters, slice_kb, slow_ratio, inject_kind, inject_xcc, inject_factor, inject_waves);
     return -1;
   }
-  const int max_launches = automatic ? 4 : 1;
   const int slots = (grid > mem_grid ? grid : mem_grid) * kPaceWaves;
   out->cus_expected = prop.multiProcessorCount;
   out->iters = iters;
@@ -361,7 +356,7 @@ int amdgpu_pace_run(int device, int blocks, int iters, int slice_kb, double slow
       std::snprintf(err, err_len, "pace check: a record holds a site out of range");
       return -1;
     }
-    if (cover.cus_reached >= out->cus_expected && cover.simds_reached >= 4 * out->cus_expected) break;
+    if (covered(cover, out->cus_expected)) break;
   }
 
   // stage 2: the fill, then pace_mem

@@ -1,7 +1,8 @@
 // The pace check's host side, shared by pace.hip and tests/native/pace_selftest.cpp: the
 // record every wave leaves, the tables and the result the reduction fills, the reduction
 // itself (located records -> per-site and per-XCD medians -> ratios, slow sites, slow XCDs)
-// and the error and note texts.  No HIP include: a plain C++17 compiler compiles it.
+// and the error and note texts.  The packed site, its text and the coverage walk are
+// ../site.h's.  No HIP include: a plain C++17 compiler compiles it.
 //
 // Only differences within one wave are ever used (cycles and ticks are each the difference
 // of two reads of one counter by one wave); nothing assumes that the counters of two XCDs agree.
@@ -12,12 +13,14 @@
 #include <cstring>
 #include <vector>
 
+#include "../site.h"
+
 extern "C" {
 
 constexpr int kPaceXccs = 16;            // HW_REG_XCC_ID is 4 bits wide
-constexpr int kPaceSiteSlots = 1 << 14;  // packed sites: simd 1:0 | cu 5:2 | sh 6 | se 9:7 | xcc 13:10
+constexpr int kPaceSiteSlots = kSiteSlots;  // packed sites (site.h)
 constexpr int kPaceWaves = 4;            // waves per workgroup: records[block * 4 + wave]
-constexpr unsigned int kPaceUnwritten = 0xFFFFFFFFu;  // site_first of a slot no wave wrote
+constexpr unsigned int kPaceUnwritten = kSiteUnwritten;  // site_first of a slot no wave wrote
 
 struct amdgpu_pace_record {  // what one wave leaves; 32 bytes
   unsigned int site_first;   // site_id() before the work
@@ -97,6 +100,11 @@ struct amdgpu_pace_result {
 
 namespace pace {
 
+using canary::format_site;
+using canary::located;
+using canary::plural;
+using canary::records_valid;
+
 constexpr double kMiB = 1048576.0;
 
 // Median of v (reordered): the middle element, or the mean of the two middle ones; 0 if empty.
@@ -107,27 +115,7 @@ inline double median(std::vector<double>& v) {
   return n % 2 ? v[n / 2] : (v[n / 2 - 1] + v[n / 2]) / 2;
 }
 
-inline bool located(const amdgpu_pace_record& r) { return r.site_first == r.site_last; }
 inline bool timed(const amdgpu_pace_record& r) { return r.ticks > 0 && r.cycles > 0 && r.work > 0; }
-
-// "xcc3/se1/sh0/cu7/simd2" of a packed site, "xcc3/se1/sh0/cu7" without simd
-inline int format_site(unsigned int site, bool simd, char* buf, int len) {
-  int n = std::snprintf(buf, len, "xcc%u/se%u/sh%u/cu%u", (site >> 10) & 0xFu, (site >> 7) & 7u, (site >> 6) & 1u,
-                        (site >> 2) & 0xFu);
-  if (simd && n > 0 && n < len) n += std::snprintf(buf + n, len - n, "/simd%u", site & 3u);
-  return n;
-}
-
-// Every written record's sites lie below kPaceSiteSlots.
-inline bool records_valid(const amdgpu_pace_record* r, int n) {
-  for (int i = 0; i < n; ++i) {
-    if (r[i].site_first == kPaceUnwritten) continue;
-    if (r[i].site_first >= static_cast<unsigned int>(kPaceSiteSlots) ||
-        r[i].site_last >= static_cast<unsigned int>(kPaceSiteSlots))
-      return false;
-  }
-  return true;
-}
 
 // The reduction.  mfma / mem: n_mfma / n_mem records in launch order (records[block * 4 + wave]
 // within a launch; unwritten slots are skipped); either may be empty.  sites (kPaceSiteSlots)
@@ -198,20 +186,9 @@ inline bool reduce(const amdgpu_pace_record* mfma, int n_mfma, const amdgpu_pace
     xcc_cpm[site >> 10].push_back(sites[site].cycles_per_mfma);
     all_cpm.push_back(sites[site].cycles_per_mfma);
   }
-  for (int cu = 0; cu < kPaceSiteSlots / 4; ++cu) {
-    bool any = false;
-    for (int simd = 0; simd < 4; ++simd) {
-      const amdgpu_pace_site_slot& s = sites[cu * 4 + simd];
-      if (s.waves == 0) continue;
-      any = true;
-      ++r.simds_reached;
-      if (s.bad) {
-        if (r.n_bad < 16) r.bad_sites[r.n_bad] = static_cast<unsigned int>(cu * 4 + simd);
-        ++r.n_bad;
-      }
-    }
-    r.cus_reached += any;
-  }
+  canary::store_coverage(canary::site_coverage([&](int s) { return sites[s].waves != 0; },
+                                               [&](int s) { return sites[s].waves != 0 && sites[s].bad != 0; }),
+                         &r);
   // slow sites: above slow_ratio x the median over sites
   if (!all_cpm.empty()) {
     r.cycles_per_mfma_median = median(all_cpm);  // sorts
@@ -299,8 +276,6 @@ inline bool reduce(const amdgpu_pace_record* mfma, int n_mfma, const amdgpu_pace
   return true;
 }
 
-inline const char* plural(unsigned long long n) { return n == 1 ? "" : "s"; }
-
 // The text of the first failing stage, in the house style:
 //   "pace check: 3 wrong results at xcc3/se1/sh0/cu7/simd2 (+1 more site)"
 //   "pace check: 2 wrong words read on xcc5 (+1 more xcc)"
@@ -374,7 +349,7 @@ inline int note(const amdgpu_pace_result& r, const amdgpu_pace_xcc_slot* xccs, c
 // pace_mfma's accumulators hold iters x (A . B) with |A . B| <= 16 * 4 * 4: exact in fp32 below 2^24.
 constexpr int kMaxIters = (1 << 24) / 256 - 1;  // 65535: the true iteration count, injection included
 constexpr int kMaxInjectFactor = 16;
-constexpr int kMaxBlocks = 4096;
+using canary::kMaxBlocks;
 constexpr int kMaxSliceKb = 16384;
 constexpr unsigned long long kMaxMemBytes = 4ull << 30;  // slices together
 

@@ -188,23 +188,15 @@ __global__ void __launch_bounds__(256) site_probe(int ksteps, int inject_check, 
 void summarize(const amdgpu_canary_site_slot* t, amdgpu_canary_sites_result* r) {
   for (int c = 0; c < kSiteChecks; ++c) r->errors[c] = 0;
   r->waves = 0;
-  r->cus_reached = r->simds_reached = r->n_bad = 0;
-  for (int cu = 0; cu < kSiteSlots / 4; ++cu) {
-    bool any = false;
-    for (int simd = 0; simd < 4; ++simd) {
-      const amdgpu_canary_site_slot& s = t[cu * 4 + simd];
-      if (s.waves == 0) continue;  // errors are only ever added together with a wave
-      any = true;
-      ++r->simds_reached;
-      r->waves += s.waves;
-      for (int c = 0; c < kSiteChecks; ++c) r->errors[c] += s.bad[c];
-      if (s.bad[0] | s.bad[1] | s.bad[2]) {
-        if (r->n_bad < 16) r->bad_sites[r->n_bad] = static_cast<unsigned int>(cu * 4 + simd);
-        ++r->n_bad;
-      }
-    }
-    r->cus_reached += any;
+  for (int i = 0; i < kSiteSlots; ++i) {
+    const amdgpu_canary_site_slot& s = t[i];
+    if (s.waves == 0) continue;  // errors are only ever added together with a wave
+    r->waves += s.waves;
+    for (int c = 0; c < kSiteChecks; ++c) r->errors[c] += s.bad[c];
   }
+  store_coverage(site_coverage([&](int i) { return t[i].waves != 0; },
+                               [&](int i) { return t[i].waves != 0 && (t[i].bad[0] | t[i].bad[1] | t[i].bad[2]) != 0; }),
+                 r);
 }
 
 }  // namespace
@@ -253,11 +245,9 @@ int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, in
   CANARY_HIP(st, ev.create());
   if (st.ok()) {
     out->cus_expected = prop.multiProcessorCount;
-    const bool automatic = blocks == 0;
-    int grid = automatic ? 2 * prop.multiProcessorCount : blocks;
-    if (grid > kMaxBlocks) grid = kMaxBlocks;
-    const int max_launches = automatic ? 4 : 1;
-    for (int l = 0; l < max_launches; ++l) {
+    const LaunchPlan plan = launch_plan(blocks, prop.multiProcessorCount, 2, true);
+    const int grid = plan.grid;
+    for (int l = 0; l < plan.max_launches; ++l) {
       float ms[1] = {0};
       time_stages(st, ev, ms, [&](int) {
         if (launch_with_max_lds(site_probe, prop, dim3(grid), dim3(kProbeWaves * kWave), ksteps,
@@ -273,7 +263,7 @@ int amdgpu_canary_sites(int device, int blocks, int ksteps, int inject_check, in
       out->ms += ms[0];
       out->launches = l + 1;
       summarize(table, out);
-      if (out->cus_reached >= out->cus_expected && out->simds_reached >= 4 * out->cus_expected) break;
+      if (covered(*out, out->cus_expected)) break;
     }
   }
   CANARY_HIP(st, d_counters.download(h_counters));

@@ -1399,12 +1399,10 @@ class PluginManager:
         from ..ops import canary
         h = self.cfg.health
         more = {}  # each option's keywords only when it is on
-        if h.canaryHostLink:
-            more.update(host_link=True, host_link_bytes=h.canaryHostLinkBytes)
-        if h.canaryPace:
-            more["pace"] = True
-        if h.canaryLdsPath:
-            more["lds_path"] = True
+        for check in canary.OPTIONAL_CHECKS:
+            if getattr(h, check.switch):
+                more[check.keyword] = True
+                more.update({arg: getattr(h, key) for arg, _, key in check.args})
         res = dict(canary.run_isolated(max(0, hip), h.canaryBytes, h.canaryTimeoutS, **more))
         if res.get("ok"):
             low = []
@@ -1618,19 +1616,17 @@ class PluginManager:
                 ("amdgpu_canary_clock_mhz", "In-kernel shader clock of the last canary run: slowest and fastest XCD."),
                 ("amdgpu_canary_xcd_pace_ratio", "Slowest XCD against the median over XCDs in the last canary run."))
         rows = {name: [] for name, _ in fams}
+        from ..ops import canary
+        error_labels = (("hbm", "hbm_errors"), ("mfma", "mfma_errors"), ("gemm", "gemm_errors"), ("lowp", "lowp_errors"),
+                        ("lds", "lds_errors"), ("site", "site_errors"), ("unreached", "cus_unreached"), ("l2", "l2_errors"),
+                        ("xcd", "xcd_errors"), ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
+                        ("reg", "reg_errors"), ("l1", "l1_errors")) + \
+            tuple(pair for check in reversed(canary.OPTIONAL_CHECKS) for pair in check.errors)  # in the order they were added
         for (gpu, part), (t, r) in runs:
             lab = 'gpu="%d",partition="%d"' % (gpu, part)
             rows["amdgpu_canary_last_run_timestamp_seconds"].append("{%s} %.3f" % (lab, t))
             rows["amdgpu_canary_last_ok"].append("{%s} %d" % (lab, int(bool(r.get("ok")))))
-            for check, key in (("hbm", "hbm_errors"), ("mfma", "mfma_errors"), ("gemm", "gemm_errors"),
-                               ("lowp", "lowp_errors"), ("lds", "lds_errors"), ("site", "site_errors"),
-                               ("unreached", "cus_unreached"), ("l2", "l2_errors"), ("xcd", "xcd_errors"),
-                               ("atomic", "atomic_errors"), ("xcd_unreached", "xcd_pairs_unreached"),
-                               ("reg", "reg_errors"), ("l1", "l1_errors"), ("host_read", "host_read_errors"),
-                               ("host_write", "host_write_errors"), ("host_copy", "host_copy_errors"),
-                               ("host_atomic", "host_atomic_errors"), ("pace", "pace_errors"),
-                               ("lds_width", "lds_width_errors"), ("lds_dma", "lds_dma_errors"),
-                               ("lds_atomic", "lds_atomic_errors"), ("lane", "lane_errors"), ("lds_tr", "tr_errors")):
+            for check, key in error_labels:
                 if key in r:
                     rows["amdgpu_canary_errors"].append('{%s,check="%s"} %d' % (lab, check, int(r[key])))
             for d, key in (("write", "write_gbps"), ("read", "read_gbps")):
