@@ -69,7 +69,7 @@ BENCH_SOURCES = ["loadgen.cpp", "bench_bindings.cpp"]  # in HARNESS_DIR
 FUZZ_TARGETS = ("pbwire", "hpack", "grpc", "http")
 FUZZ_DIR = os.path.join(HARNESS_DIR, "fuzz")
 OPS_DIR = os.path.join(PKG_DIR, "ops")
-CANARY_HEADERS = [os.path.join(OPS_DIR, f) for f in ("canary_common.h", "canary_host.h", "site.h")]
+CANARY_HEADERS = [os.path.join(OPS_DIR, f) for f in ("canary_common.h", "canary_host.h", "mfma_forms.h", "site.h")]
 
 
 def _hip_lib(name: str, subdir: str, sources, headers):

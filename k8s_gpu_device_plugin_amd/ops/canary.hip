@@ -14,9 +14,9 @@
 //      Write and read passes are timed separately -> achieved HBM GB/s (hbm.hip).
 //   2. MFMA exactness    - v_mfma_f32_32x32x16_bf16 on small-integer operands
 //      (exact in bf16 and fp32) checked lane-by-lane against a scalar reference
-//      using the documented gfx950 fragment maps (cdna_hip_programming.md §3).
+//      using the documented gfx950 fragment maps (form_check<FormBf16>, mfma_forms.h).
 //   3. MFMA throughput   - register-resident 32x32x16 bf16 MFMA chains, 4 waves
-//      per block (one per SIMD), 8 blocks per CU -> dense bf16 TFLOP/s.
+//      per block (one per SIMD), 8 blocks per CU -> dense bf16 TFLOP/s (rate_chain<FormBf16>).
 //   4. Matrix path       - LDS-staged MFMA GEMM on exact integer data, ABFT-checked (gemm.hip).
 //   5. fp8 / bf8 / fp4 MFMA exactness and rate, LDS march (datapath.hip).
 //   6. Site probe        - MFMA and vector-ALU exactness on every CU and SIMD, with the
@@ -29,7 +29,7 @@
 //
 // This file holds the two MFMA probes (2, 3) and amdgpu_canary_run, which runs checks 1-7 in
 // that order.  The C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py) is declared in
-// canary_common.h, the host-side helpers every source shares in canary_host.h.
+// canary_common.h, the host-side helpers in canary_host.h, the MFMA forms in mfma_forms.h.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -42,55 +42,18 @@ namespace {
 
 using namespace canary;
 
-// One wave per block computes C[32x32] = A[32xK] * B[Kx32] with K = 16 * ksteps, then
-// every lane checks its 16 accumulator registers against a scalar integer reference.
-// Blocks below `inject_blocks` perturb one A operand (lane 0, first k-step): the fault
-// injection that proves the verifier sees a wrong matrix-core result.
+// One wave per block runs the bf16 form's exactness check, K = 16 * ksteps.  Blocks below `inject_blocks`
+// perturb one A operand: the fault injection that proves the verifier sees a wrong matrix-core result.
 __global__ void __launch_bounds__(64) mfma_exact(int ksteps, int inject_blocks,
                                                  unsigned long long* __restrict__ errors) {
   const int lane = threadIdx.x;
-  const int r = lane & 31, h = lane >> 5;
   const uint32_t blk = blockIdx.x;
-  f32x16 acc = zero_f32x16();
-  for (int s = 0; s < ksteps; ++s) {
-    bf16x8 a, b;
-    for (int j = 0; j < 8; ++j) {
-      const int k = s * 16 + 8 * h + j;  // lane l holds A[r][8h+j], B[8h+j][r]
-      a[j] = bf16_of_int(a_val(blk, r, k) + ((s == 0 && j == 0 && lane == 0 && static_cast<int>(blk) < inject_blocks)
-                                                   ? 1 : 0));
-      b[j] = bf16_of_int(b_val(blk, k, r));
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-  }
-  uint32_t bad = 0;
-  const int col = lane & 31;
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = cd_row32(reg, h);
-    int ref = 0;
-    for (int k = 0; k < ksteps * 16; ++k) ref += a_val(blk, row, k) * b_val(blk, k, col);
-    bad += acc[reg] != static_cast<float>(ref);
-  }
+  uint32_t bad = form_check<FormBf16>(blk, lane, ksteps, 0, static_cast<int>(blk) < inject_blocks);
   wave_sum(bad);
   if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
 }
 
-// Throughput: register-resident operands, two independent accumulator chains per wave.
-__global__ void __launch_bounds__(256) mfma_rate(int iters, float* __restrict__ sink) {
-  const int lane = threadIdx.x & 63;
-  bf16x8 a, b;
-  for (int j = 0; j < 8; ++j) {
-    a[j] = bf16_of_int(((lane + j) % 5) - 2);
-    b[j] = bf16_of_int(((lane * 3 + j) % 7) - 3);
-  }
-  f32x16 acc0 = zero_f32x16(), acc1 = zero_f32x16();
-  for (int it = 0; it < iters; ++it) {
-    acc0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc0, 0, 0, 0);
-    acc1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b, a, acc1, 0, 0, 0);
-  }
-  float s = 0.f;
-  for (int i = 0; i < 16; ++i) s += acc0[i] + acc1[i];
-  if (s == 1234.5f) sink[blockIdx.x * blockDim.x + threadIdx.x] = s;  // keeps the chain live
-}
+constexpr auto mfma_rate = rate_chain<FormBf16>;  // the kernel (mfma_forms.h)
 
 }  // namespace
 
@@ -117,7 +80,7 @@ int amdgpu_canary_run(int device, unsigned long long hbm_bytes, int passes, int 
   Events<3> ev;
   const uint64_t n = hbm_bytes / sizeof(uint4);
   unsigned long long h_err[2] = {0, 0};
-  float t_write = 0, t_read = 0, t_mfma[1] = {0};
+  float t_write = 0, t_read = 0, t_mfma = 0;
   if (passes < 1) passes = 1;
   CANARY_HIP(st, hipSetDevice(device), "hipSetDevice: ");
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties: ");
@@ -139,26 +102,17 @@ int amdgpu_canary_run(int device, unsigned long long hbm_bytes, int passes, int 
     st.check(hipGetLastError());
   }
   // 3. MFMA rate
-  CANARY_HIP(st, sink.alloc(static_cast<size_t>(prop.multiProcessorCount) * 8 * 256 * sizeof(float)), "hipMalloc: ");
-  if (st.ok()) {
-    st.stage("mfma_rate: ");
-    hipLaunchKernelGGL(mfma_rate, dim3(prop.multiProcessorCount * 8), dim3(256), 0, 0, 16, sink.get());  // warm-up
-    time_stages(st, ev, t_mfma, [&](int) {
-      hipLaunchKernelGGL(mfma_rate, dim3(prop.multiProcessorCount * 8), dim3(256), 0, 0, mfma_iters, sink.get());
-      return hipSuccess;
-    });
-  }
+  CANARY_HIP(st, alloc_rate_sink(sink, rate_blocks(prop)), "hipMalloc: ");
+  st.stage("mfma_rate: ");
+  t_mfma = time_rate_launch(st, ev, mfma_rate, rate_blocks(prop), mfma_iters, sink.get());
   CANARY_HIP(st, d_err.download(h_err), "hipMemcpy: ");
   if (st.report("", out->error, sizeof(out->error)) != 0) return -1;
   out->hbm_errors = h_err[0];
   out->mfma_errors = h_err[1];
   out->write_gbps = static_cast<double>(n) * sizeof(uint4) * passes / (t_write * 1e-3) / 1e9;
   out->read_gbps = static_cast<double>(n) * sizeof(uint4) * passes / (t_read * 1e-3) / 1e9;
-  {
-    const double flops = 2.0 * 32 * 32 * 16 * 2.0 /*chains*/ * mfma_iters * (prop.multiProcessorCount * 8.0 * 4 /*waves*/);
-    out->mfma_tflops = flops / (t_mfma[0] * 1e-3) / 1e12;
-  }
-  out->elapsed_ms = t_write + t_read + t_mfma[0];
+  out->mfma_tflops = rate_tflops<FormBf16>(mfma_iters, rate_blocks(prop), t_mfma);
+  out->elapsed_ms = t_write + t_read + t_mfma;
   // 4. matrix path: HBM -> L2 -> LDS DMA -> ds_read -> MFMA, exact and checksummed.  4096^3
   // (256 tiles of 256x256: one per CU) takes ~0.5 ms; hbm_bytes < 256 MiB (fault-injection
   // runs) uses 1024^3 on the 128x128 kernel.

@@ -1,11 +1,10 @@
 // Shared by every gfx950 canary source (canary.hip, hbm.hip, gemm.hip, datapath.hip,
 // sites.hip, fabric.hip, cumem.hip) and, through canary_host.h, by the libraries of the
-// host-link, pace and LDS-path checks.  Device side: the hash that derives exact small-integer
-// operands, the MFMA register vector types and the 32x32 C/D row map, the bf16 / OCP
-// low-precision operand packing, the s_getreg immediates, site_id(), the wave and block error reductions.  And the C ABI,
-// declared here once: every result struct that canary.py mirrors with ctypes, with its size
-// pinned, and the prototype of every exported entry point that another source calls.  The
-// host-side helpers are in canary_host.h, the packed site and kMaxBlocks in site.h.
+// host-link, pace and LDS-path checks.  Device side: the s_getreg immediates, site_id(), the
+// wave and block error reductions.  And the C ABI, declared here once: every result struct that
+// canary.py mirrors with ctypes, with its size pinned, and the prototype of every exported entry
+// point that another source calls.  The host-side helpers are in canary_host.h, the packed site
+// and kMaxBlocks in site.h, the operand hash, MFMA vector types, lane maps and forms in mfma_forms.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,102 +16,17 @@ namespace canary {
 
 constexpr int kWave = 64;
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-
-// C/D map of the 32x32 MFMA forms (cdna_hip_programming.md §3; it does not depend on the
-// operand type): accumulator register `reg` (0-15) of a lane in half h = lane >> 5 is the
-// element of this row in column lane & 31.
-__device__ __forceinline__ int cd_row32(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-// A zeroed accumulator.  lowp_rate and lowp_gemm (datapath.hip) spell the loop out instead:
-// with the call the compiler schedules or allocates those two differently (as with wave_sum below).
-__device__ __forceinline__ f32x16 zero_f32x16() {
-  f32x16 v;
-  for (int i = 0; i < 16; ++i) v[i] = 0.f;
-  return v;
-}
-
 // s_getreg_b32 immediate: register id 5:0, bit offset 10:6, size - 1 15:11
 constexpr int kHwRegHwId = 4, kHwRegXccId = 20;
 constexpr int getreg_imm(int reg, int offset, int size) { return ((size - 1) << 11) | (offset << 6) | reg; }
 
-__device__ __forceinline__ uint32_t mix32(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return static_cast<uint32_t>(x);
-}
-
-// small integer in [-4, 4] from a hash: exactly representable in bf16, fp8 (e4m3 and
-// e5m2) and fp4 (e2m1), so MFMA results on such operands are exact in fp32
-__device__ __forceinline__ int small_int(uint64_t key) { return static_cast<int>(mix32(key) % 9u) - 4; }
-
-// A[row][k] and B[k][col] of exactness block `blk`
-__device__ __forceinline__ int a_val(uint32_t blk, int row, int k) {
-  return small_int((static_cast<uint64_t>(blk) << 40) ^ (static_cast<uint64_t>(row) << 20) ^ static_cast<uint64_t>(k));
-}
-__device__ __forceinline__ int b_val(uint32_t blk, int k, int col) {
-  return small_int(0x5555ull ^ (static_cast<uint64_t>(blk) << 40) ^ (static_cast<uint64_t>(k) << 20) ^
-                   static_cast<uint64_t>(col) ^ (1ull << 62));
-}
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-
-__device__ __forceinline__ short bf16_of_int(int v) {
-  const float f = static_cast<float>(v);
-  uint32_t u;
-  __builtin_memcpy(&u, &f, 4);
-  return static_cast<short>(u >> 16);  // exact for small integers
-}
-
-using i32x8 = __attribute__((ext_vector_type(8))) int;
 using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
-
-constexpr int kFp8 = 0, kBf8 = 1, kFp4 = 4;  // cbsz / blgp format codes
-constexpr int kFp8Unscaled = 8;             // host-side id of v_mfma_f32_32x32x16_fp8_fp8
-
-// OCP code of a small integer v in [-4, 4] (every one is exact in all three formats).
-template <int FMT>
-__device__ __forceinline__ uint32_t lowp_code(int v) {
-  const uint32_t m = static_cast<uint32_t>(v < 0 ? -v : v);
-  uint32_t c;
-  if (FMT == kFp8) c = m == 0 ? 0u : m == 1 ? 0x38u : m == 2 ? 0x40u : m == 3 ? 0x44u : 0x48u;       // e4m3fn
-  else if (FMT == kBf8) c = m == 0 ? 0u : m == 1 ? 0x3Cu : m == 2 ? 0x40u : m == 3 ? 0x42u : 0x44u;  // e5m2
-  else c = m == 0 ? 0u : m == 1 ? 0x2u : m == 2 ? 0x4u : m == 3 ? 0x5u : 0x6u;                       // e2m1
-  if (v < 0) c |= FMT == kFp4 ? 0x8u : 0x80u;
-  return c;
-}
-
-template <int FMT>
-constexpr int kBits = FMT == kFp4 ? 4 : 8;
-
-// k (within one 64-deep step) of element j of a lane in half h (layout note in datapath.hip)
-template <int FMT>
-__device__ __forceinline__ int kmap(int h, int j) {
-  return FMT == kFp4 ? 32 * h + j : 32 * (j >> 4) + 16 * h + (j & 15);
-}
-
-// element j (0..31) of a lane's operand
-template <int FMT>
-__device__ __forceinline__ void put(i32x8& x, int j, uint32_t code) {
-  constexpr int b = kBits<FMT>;
-  x[(j * b) >> 5] |= static_cast<int>(code << ((j * b) & 31));
-}
-
-// E8M0 block scale of (row or column `rc`, k-block `kb`, operand `which`) when varied:
-// 2^0 or 2^1, so every product stays an exact small integer in fp32.
-__device__ __forceinline__ int scale_exp(int vary, int rc, int kb, int which) {
-  return vary ? static_cast<int>(mix32((static_cast<uint64_t>(which) << 48) ^ (static_cast<uint64_t>(rc) << 24) ^
-                                       static_cast<uint64_t>(kb)) & 1u)
-              : 0;
-}
 
 // Sum over the wave; lane 0 holds it.  One loop, two spellings: which one a kernel calls changes
 // the registers the compiler allocates and how it unrolls the kernel's other loops (mfma_exact:
-// 32 VGPRs in place, 46 by value).  In place: mfma_exact, lowp_exact, fp8_exact, lds_march; by
-// value: all others.  Compare the kernel-resource-usage remarks before changing a call site.
+// 32 VGPRs in place, 48 by value).  In place: mfma_exact, lowp_exact, fp8_exact (datapath.hip's
+// exact_block), lds_march; by value: all others.  Compare the kernel-resource-usage remarks before
+// changing a call site (tests/test_canary_forms.py pins canary.hip's, datapath.hip's and sites.hip's).
 __device__ __forceinline__ void wave_sum(uint32_t& v) {
   for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
 }

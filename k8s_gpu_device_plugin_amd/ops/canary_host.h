@@ -11,6 +11,7 @@
 #include <cstdio>
 
 #include "canary_common.h"
+#include "mfma_forms.h"
 
 namespace canary {
 
@@ -132,6 +133,33 @@ long long count_errors(int device, Launch&& launch) {
   CANARY_HIP(st, hipDeviceSynchronize());
   CANARY_HIP(st, d_errors.download(&h));
   return st.ok() ? static_cast<long long>(h) : -1;
+}
+
+// ---- the MFMA rate launches (rate_chain<F>, mfma_forms.h): 8 blocks of 4 waves per CU ----
+constexpr int kRateThreads = 256;
+inline int rate_blocks(const hipDeviceProp_t& prop) { return prop.multiProcessorCount * 8; }
+inline hipError_t alloc_rate_sink(DeviceBuffer<float>& sink, int blocks) {
+  return sink.alloc(static_cast<size_t>(blocks) * kRateThreads * sizeof(float));
+}
+
+// Device ms of one launch of `kernel` with `iters` MFMA pairs per wave, after a warm-up of 16; 0 on a HIP error.
+template <typename Ev, typename Kernel>
+float time_rate_launch(Status& st, const Ev& ev, Kernel kernel, int blocks, int iters, float* sink) {
+  float ms[1] = {0};
+  if (!st.ok()) return 0;
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRateThreads), 0, 0, 16, sink);  // warm-up
+  time_stages(st, ev, ms, [&](int) {
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kRateThreads), 0, 0, iters, sink);
+    return hipSuccess;
+  });
+  return st.ok() ? ms[0] : 0;
+}
+
+// Dense TFLOP/s of such a launch of form F that took `ms` (0 when ms is): 2 * 32 * 32 * K flop per MFMA.
+template <class F>
+double rate_tflops(int iters, int blocks, float ms) {
+  const double flops = 2.0 * 32 * 32 * F::kK * 2.0 /*chains*/ * iters * (blocks * (kRateThreads / kWave));
+  return ms > 0 ? flops / (ms * 1e-3) / 1e12 : 0;
 }
 
 constexpr int kMaxLdsBytes = 160 * 1024;

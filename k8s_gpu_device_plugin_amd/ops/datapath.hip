@@ -9,28 +9,17 @@
 // these, so a partition is advertised healthy only if they are exact too:
 //
 //   1. Exactness: one wave per block computes C[32x32] = A[32xK] * B[Kx32] from small
-//      integers (exact in every format, canary_common.h) with per-lane power-of-two
-//      block scales, then checks every accumulator register against a scalar integer
-//      reference.  Blocks below `inject_blocks` perturb one operand: the fault
-//      injection that proves the verifier sees a wrong result.
-//   2. Rate: register-resident MFMA chains, 8 blocks of 4 waves per CU -> TFLOP/s.
+//      integers (exact in every format) with per-lane power-of-two block scales, then checks
+//      every accumulator register against a scalar integer reference (form_check<F>).  Blocks
+//      below `inject_blocks` perturb one operand: the fault injection that proves the verifier
+//      sees a wrong result.
+//   2. Rate: register-resident MFMA chains, 8 blocks of 4 waves per CU -> TFLOP/s (rate_chain<F>).
 //   3. LDS march: every workgroup takes its CU's whole LDS (160 KB on gfx950), writes
 //      an address-derived pattern, reads it back in reverse order (words written by
 //      another wave, so addressing faults show) while writing the complement, then
 //      reads the complement (both polarities of every bit).
 //
-// Operand and scale layout of the scaled 32x32x64 form, measured on the MI355X with raw
-// fragments (scripts/probe_lowp_layout.py, profiles/r2/lowp_layout_probe.json): lane l
-// (r = l & 31, h = l >> 5) holds 32 elements of row r of A (column r of B), byte j of the
-// 8-dword operand for fp8/bf8, nibble j of the low 4 dwords for fp4, and its scale
-// operand (byte 0, op_sel 0) is the E8M0 exponent of k-block h of that row:
-//   * fp4:     element j is k = 32 h + j (the lane's 32 elements are its own block);
-//   * fp8/bf8: element j is k = 32 (j >> 4) + 16 h + (j & 15), i.e. two K=32 halves, each
-//     in the 32x32x16 map, so block h spans elements 16h..16h+15 of BOTH lane halves.
-// A and B use the same map, C/D the dtype-independent 32x32 one (cd_row32 in
-// canary_common.h).  tests/test_gpu_datapath.py checks it against a PyTorch fp32 GEMM on random codes
-// and random block scales, which only matches if both maps are right.
-//
+// The forms, their operand and scale layout, form_check and rate_chain: mfma_forms.h.
 // C ABI for ctypes (k8s_gpu_device_plugin_amd/ops/canary.py).
 #include <hip/hip_runtime.h>
 
@@ -42,96 +31,30 @@
 
 namespace {
 
-using namespace canary;  // operand packing (lowp_code, kmap, put, scale_exp): canary_common.h
+using namespace canary;
+
+// One wave per block runs the exactness check of form F; blocks below `inject_blocks` perturb one operand.
+template <class F>
+__device__ __forceinline__ void exact_block(int ksteps, int vary_scale, int inject_blocks,
+                                            unsigned long long* __restrict__ errors) {
+  const int lane = threadIdx.x;
+  uint32_t bad = form_check<F>(blockIdx.x, lane, ksteps, vary_scale, static_cast<int>(blockIdx.x) < inject_blocks);
+  wave_sum(bad);
+  if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
+}
 
 template <int FMT>
 __global__ void __launch_bounds__(64) lowp_exact(int ksteps, int vary_scale, int inject_blocks,
                                                  unsigned long long* __restrict__ errors) {
-  const int lane = threadIdx.x;
-  const int r = lane & 31, h = lane >> 5;
-  const uint32_t blk = blockIdx.x + (static_cast<uint32_t>(FMT + 1) << 20);  // distinct data per format
-  f32x16 acc = zero_f32x16();
-  for (int s = 0; s < ksteps; ++s) {
-    i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int k = 64 * s + kmap<FMT>(h, j);
-      int av = a_val(blk, r, k);
-      if (s == 0 && j == 0 && lane == 0 && static_cast<int>(blockIdx.x) < inject_blocks) av = av == 4 ? 3 : av + 1;
-      put<FMT>(a, j, lowp_code<FMT>(av));
-      put<FMT>(b, j, lowp_code<FMT>(b_val(blk, k, r)));
-    }
-    const int sa = 127 + scale_exp(vary_scale, r, 2 * s + h, 0);
-    const int sb = 127 + scale_exp(vary_scale, r, 2 * s + h, 1);
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, FMT, FMT, 0, sa, 0, sb);
-  }
-  uint32_t bad = 0;
-  const int col = lane & 31;
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = cd_row32(reg, h);
-    int ref = 0;
-    for (int kb = 0; kb < 2 * ksteps; ++kb) {
-      int part = 0;
-      for (int j = 0; j < 32; ++j) part += a_val(blk, row, 32 * kb + j) * b_val(blk, 32 * kb + j, col);
-      ref += part << (scale_exp(vary_scale, row, kb, 0) + scale_exp(vary_scale, col, kb, 1));
-    }
-    bad += acc[reg] != static_cast<float>(ref);
-  }
-  wave_sum(bad);
-  if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
+  exact_block<FormScaled<FMT>>(ksteps, vary_scale, inject_blocks, errors);
 }
 
-// Non-scaled fp8: lane l holds A[r][16 s + 8 h + j] / B[16 s + 8 h + j][r], byte j of a
-// 2-dword operand (the bf16 32x32x16 map with one byte per element).
 __global__ void __launch_bounds__(64) fp8_exact(int ksteps, int inject_blocks, unsigned long long* __restrict__ errors) {
-  const int lane = threadIdx.x;
-  const int r = lane & 31, h = lane >> 5;
-  const uint32_t blk = blockIdx.x + (0x77u << 20);
-  f32x16 acc = zero_f32x16();
-  for (int s = 0; s < ksteps; ++s) {
-    uint64_t a = 0, b = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const int k = 16 * s + 8 * h + j;
-      int av = a_val(blk, r, k);
-      if (s == 0 && j == 0 && lane == 0 && static_cast<int>(blockIdx.x) < inject_blocks) av = av == 4 ? 3 : av + 1;
-      a |= static_cast<uint64_t>(lowp_code<kFp8>(av)) << (8 * j);
-      b |= static_cast<uint64_t>(lowp_code<kFp8>(b_val(blk, k, r))) << (8 * j);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_fp8_fp8(static_cast<long>(a), static_cast<long>(b), acc, 0, 0, 0);
-  }
-  uint32_t bad = 0;
-  const int col = lane & 31;
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = cd_row32(reg, h);
-    int ref = 0;
-    for (int k = 0; k < ksteps * 16; ++k) ref += a_val(blk, row, k) * b_val(blk, k, col);
-    bad += acc[reg] != static_cast<float>(ref);
-  }
-  wave_sum(bad);
-  if (lane == 0 && bad) atomicAdd(errors, static_cast<unsigned long long>(bad));
+  exact_block<FormFp8Unscaled>(ksteps, 0, inject_blocks, errors);
 }
 
-// Throughput: register-resident operands, two independent accumulator chains per wave.
 template <int FMT>
-__global__ void __launch_bounds__(256) lowp_rate(int iters, float* __restrict__ sink) {
-  const int lane = threadIdx.x & 63;
-  i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    put<FMT>(a, j, lowp_code<FMT>(((lane + j) % 5) - 2));
-    put<FMT>(b, j, lowp_code<FMT>(((lane * 3 + j) % 7) - 3));
-  }
-  f32x16 acc0, acc1;
-  for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0.f;
-  for (int it = 0; it < iters; ++it) {
-    acc0 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc0, FMT, FMT, 0, 127, 0, 127);
-    acc1 = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(b, a, acc1, FMT, FMT, 0, 127, 0, 127);
-  }
-  float s = 0.f;
-  for (int i = 0; i < 16; ++i) s += acc0[i] + acc1[i];
-  if (s == 1234.5f) sink[blockIdx.x * blockDim.x + threadIdx.x] = s;  // keeps the chains live
-}
+constexpr auto lowp_rate = rate_chain<FormScaled<FMT>>;  // the kernel (mfma_forms.h)
 
 // C[MxN] (fp32) = dequant(A)[MxK] * dequant(Bt)[NxK]^T with one E8M0 scale per 32 k:
 // A, Bt hold one OCP code per byte (fp4 in the low nibble), sa [M][K/32], sb [N][K/32].
@@ -149,12 +72,8 @@ __global__ void __launch_bounds__(64) lowp_gemm(const uint8_t* __restrict__ A, c
   for (int k0 = 0; k0 < K; k0 += 64) {
     const uint8_t* ap = A + static_cast<size_t>(m0 + r) * K + k0;
     const uint8_t* bp = Bt + static_cast<size_t>(n0 + r) * K + k0;
-    i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      put<FMT>(a, j, ap[kmap<FMT>(h, j)] & (FMT == kFp4 ? 0xFu : 0xFFu));
-      put<FMT>(b, j, bp[kmap<FMT>(h, j)] & (FMT == kFp4 ? 0xFu : 0xFFu));
-    }
+    const auto at = [h](int j) { return kmap<FMT>(h, j); };
+    const i32x8 a = raw_operand<FMT>(ap, at), b = raw_operand<FMT>(bp, at);
     const int ka = sa[static_cast<size_t>(m0 + r) * kblocks + k0 / 32 + h];
     const int kb = sb[static_cast<size_t>(n0 + r) * kblocks + k0 / 32 + h];
     acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, FMT, FMT, 0, ka, 0, kb);
@@ -173,12 +92,8 @@ __global__ void __launch_bounds__(64) lowp_raw(const uint8_t* __restrict__ a, co
                                                const uint8_t* __restrict__ sa, const uint8_t* __restrict__ sb,
                                                float* __restrict__ C) {
   const int lane = threadIdx.x;
-  i32x8 x = {0, 0, 0, 0, 0, 0, 0, 0}, y = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < 32; ++j) {
-    put<FMT>(x, j, a[lane * 32 + j] & (FMT == kFp4 ? 0xFu : 0xFFu));
-    put<FMT>(y, j, b[lane * 32 + j] & (FMT == kFp4 ? 0xFu : 0xFFu));
-  }
+  const auto at = [](int j) { return j; };
+  const i32x8 x = raw_operand<FMT>(a + lane * 32, at), y = raw_operand<FMT>(b + lane * 32, at);
   f32x16 acc = zero_f32x16();
   acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(x, y, acc, FMT, FMT, 0, sa[lane], 0, sb[lane]);
   for (int reg = 0; reg < 16; ++reg) {
@@ -227,20 +142,14 @@ K by_format(int fmt, K fp8, K bf8, K fp4) {
   return fmt == kFp8 ? fp8 : fmt == kBf8 ? bf8 : fmt == kFp4 ? fp4 : nullptr;
 }
 
-// Device ms of one lowp_rate launch of `iters` MFMA pairs per wave, after a warm-up one; 0 on a
-// HIP error or an unknown format.
-float time_lowp_rate(Status& st, int fmt, int blocks, int iters, float* sink) {
+// Dense TFLOP/s of the block-scaled form `fmt` from one timed launch; 0 on a HIP error or an unknown format.
+double lowp_rate_tflops(Status& st, int fmt, int blocks, int iters, float* sink) {
   const auto kernel = by_format(fmt, lowp_rate<kFp8>, lowp_rate<kBf8>, lowp_rate<kFp4>);
   Events<2> ev;
-  float ms[1] = {0};
   CANARY_HIP(st, ev.create());
-  if (!st.ok() || kernel == nullptr) return 0;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0, 16, sink);  // warm-up
-  time_stages(st, ev, ms, [&](int) {
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), 0, 0, iters, sink);
-    return hipSuccess;
-  });
-  return st.ok() ? ms[0] : 0;
+  if (kernel == nullptr) return 0;
+  static_assert(FormScaled<kFp8>::kK == FormScaled<kBf8>::kK && FormScaled<kFp8>::kK == FormScaled<kFp4>::kK);
+  return rate_tflops<FormScaled<kFp8>>(iters, blocks, time_rate_launch(st, ev, kernel, blocks, iters, sink));
 }
 
 bool launch_lowp_exact(int fmt, int blocks, int ksteps, int vary, int inject, unsigned long long* d_err) {
@@ -271,7 +180,7 @@ int amdgpu_canary_datapaths(int device, int iters, amdgpu_canary_datapath_result
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
   CANARY_HIP(st, d_err.alloc(sizeof(h_err)));
   CANARY_HIP(st, d_err.zero());
-  CANARY_HIP(st, sink.alloc(static_cast<size_t>(prop.multiProcessorCount) * 8 * 256 * sizeof(float)));
+  CANARY_HIP(st, alloc_rate_sink(sink, rate_blocks(prop)));
   for (int fmt : {kFp8, kBf8, kFp4, kFp8Unscaled})
     if (st.ok() && !launch_lowp_exact(fmt, prop.multiProcessorCount * 2, 4, 1, 0, d_err.get())) st.fail("");
   if (st.ok()) {
@@ -283,13 +192,9 @@ int amdgpu_canary_datapaths(int device, int iters, amdgpu_canary_datapath_result
   if (st.ok()) {
     out->lowp_errors = h_err[0];
     out->lds_errors = h_err[1];
-    const int blocks = prop.multiProcessorCount * 8;
     if (iters < 1) iters = 1;
-    const double flops = 2.0 * 32 * 32 * 64 * 2.0 /*chains*/ * iters * (blocks * 4.0 /*waves*/);
-    const float t8 = time_lowp_rate(st, kFp8, blocks, iters, sink.get());
-    const float t4 = time_lowp_rate(st, kFp4, blocks, iters, sink.get());
-    out->fp8_tflops = t8 > 0 ? flops / (t8 * 1e-3) / 1e12 : 0;
-    out->fp4_tflops = t4 > 0 ? flops / (t4 * 1e-3) / 1e12 : 0;
+    out->fp8_tflops = lowp_rate_tflops(st, kFp8, rate_blocks(prop), iters, sink.get());
+    out->fp4_tflops = lowp_rate_tflops(st, kFp4, rate_blocks(prop), iters, sink.get());
   }
   return st.report("datapaths: ", err, err_len);
 }
@@ -313,14 +218,10 @@ int amdgpu_canary_lowp_rate(int device, int fmt, int iters, double* tflops) {
   DeviceBuffer<float> sink;
   CANARY_HIP(st, hipSetDevice(device));
   CANARY_HIP(st, hipGetDeviceProperties(&prop, device));
+  CANARY_HIP(st, alloc_rate_sink(sink, rate_blocks(prop)));
   if (!st.ok()) return -1;
-  const int blocks = prop.multiProcessorCount * 8;
-  CANARY_HIP(st, sink.alloc(static_cast<size_t>(blocks) * 256 * sizeof(float)));
-  if (!st.ok()) return -1;
-  const float ms = time_lowp_rate(st, fmt, blocks, iters, sink.get());
-  if (ms <= 0) return -1;
-  *tflops = 2.0 * 32 * 32 * 64 * 2.0 * iters * (blocks * 4.0) / (ms * 1e-3) / 1e12;
-  return 0;
+  *tflops = lowp_rate_tflops(st, fmt, rate_blocks(prop), iters, sink.get());
+  return *tflops > 0 ? 0 : -1;
 }
 
 // LDS march mismatches over 2 workgroups per CU (`inject_blocks` of them flip one bit);

@@ -204,15 +204,6 @@ __host__ __device__ constexpr int table_offset(int op) {  // tables back to back
 constexpr int kTablesBytes = table_offset(kAtomicOps);
 constexpr int kCappedOffset = kTablesBytes;  // one more word: CAS loops that ran out of retries
 
-__host__ __device__ inline uint64_t fmix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
-
 // The row of 64 consecutive elements that wave `wave` (global index) hits at `step`, lane l
 // taking element 64 * row + l: one wave-instruction covers 256 (or 512) contiguous bytes.
 // The CAS loop takes word hash & 63 of the same hash.

@@ -9,6 +9,8 @@
 #include <cstring>
 #include <vector>
 
+#include "../mfma_forms.h"
+
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define HOSTLINK_HD __host__ __device__
 #else
@@ -104,14 +106,7 @@ constexpr int kTablesBytes = table_offset(kLinkOps);
 constexpr int kCappedOffset = kTablesBytes;  // one more u32: CAS loops that ran out of retries
 constexpr int kTablesAlloc = kTablesBytes + 256;
 
-HOSTLINK_HD inline uint64_t fmix64(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return x;
-}
+using canary::fmix64;  // ../mfma_forms.h
 
 // As in ops/fabric.hip: wave `wave` (global index) hits one row of 64 consecutive elements,
 // lane l taking element 64 * row + l.  The CAS loop and the swap take word hash & 63.

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../mfma_forms.h"
 #include "../site.h"
 
 #ifdef __HIPCC__
@@ -86,14 +87,7 @@ constexpr uint32_t kInjectBit = 1u << 9;
 constexpr int kInjectLane = 3;
 constexpr int kInjectKinds = 6;  // 0 lds, 1 subword, 2 dma, 3 atomic, 4 lane, 5 tr
 
-LDSPATH_HD uint32_t mix32(uint64_t x) {
-  x ^= x >> 33;
-  x *= 0xff51afd7ed558ccdull;
-  x ^= x >> 33;
-  x *= 0xc4ceb9fe1a85ec53ull;
-  x ^= x >> 33;
-  return static_cast<uint32_t>(x);
-}
+using canary::mix32;  // the hash of mfma_forms.h
 
 // ---- stage 1: lds_widths -------------------------------------------------------------------
 // Word i of the region under seed s (s already folds in the launch seed, the block and the rep).

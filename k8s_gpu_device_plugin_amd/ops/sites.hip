@@ -8,12 +8,12 @@
 //
 //   * site_id(): (xcc, se, sh, cu, simd) from HW_REG_HW_ID bits 15:4 and HW_REG_XCC_ID
 //     bits 3:0 (layout: hip/amd_detail/amd_device_functions.h above __smid()), packed into
-//     14 bits (canary_common.h).  Read before and after the checks; a wave whose site
+//     14 bits (canary_common.h, site.h).  Read before and after the checks; a wave whose site
 //     changed in between (context-switched to other hardware) is counted as moved and its
 //     errors as unlocated.
-//   * mfma: v_mfma_f32_32x32x16_bf16 on small integers, as mfma_exact (K = 16 * ksteps);
-//   * lowp: v_mfma_scale_f32_32x32x64_f8f6f4 in fp8 with varied power-of-two block scales,
-//     as lowp_exact<fp8> (K = 64 * ksteps);
+//   * mfma: v_mfma_f32_32x32x16_bf16 on small integers: mfma_exact's form_check<FormBf16> (K = 16 * ksteps);
+//   * lowp: v_mfma_scale_f32_32x32x64_f8f6f4 in fp8 with varied power-of-two block scales:
+//     lowp_exact<fp8>'s form_check<FormScaled<kFp8>> of mfma_forms.h (K = 64 * ksteps);
 //   * valu: a fixed per-lane chain of 32-bit multiply-add / shift / rotate, 64-bit add,
 //     exact fp32 and fp64 FMA and a __shfl_xor butterfly, folded into one 32-bit digest
 //     per lane and compared with digests the HOST computed with the same function: a
@@ -88,61 +88,7 @@ void valu_expected(uint32_t* digest) {  // the 64 lanes of one wave, shuffle emu
   for (int l = 0; l < kWave; ++l) digest[l] = valu_digest(s[l]);
 }
 
-// ---- the three checks: wrong results this lane sees --------------------------------
-__device__ __forceinline__ uint32_t check_mfma(uint32_t key, int lane, int ksteps, bool inject) {
-  const int r = lane & 31, h = lane >> 5;
-  f32x16 acc = zero_f32x16();
-  for (int s = 0; s < ksteps; ++s) {
-    bf16x8 a, b;
-    for (int j = 0; j < 8; ++j) {
-      const int k = s * 16 + 8 * h + j;  // lane l holds A[r][8h+j], B[8h+j][r]
-      a[j] = bf16_of_int(a_val(key, r, k) + ((s == 0 && j == 0 && lane == 0 && inject) ? 1 : 0));
-      b[j] = bf16_of_int(b_val(key, k, r));
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
-  }
-  uint32_t bad = 0;
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = cd_row32(reg, h);
-    int ref = 0;
-    for (int k = 0; k < ksteps * 16; ++k) ref += a_val(key, row, k) * b_val(key, k, r);
-    bad += acc[reg] != static_cast<float>(ref);
-  }
-  return bad;
-}
-
-__device__ __forceinline__ uint32_t check_lowp(uint32_t key, int lane, int ksteps, bool inject) {
-  const int r = lane & 31, h = lane >> 5;
-  const uint32_t blk = key + (static_cast<uint32_t>(kFp8 + 1) << 20);  // as lowp_exact<kFp8>
-  f32x16 acc = zero_f32x16();
-  for (int s = 0; s < ksteps; ++s) {
-    i32x8 a = {0, 0, 0, 0, 0, 0, 0, 0}, b = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < 32; ++j) {
-      const int k = 64 * s + kmap<kFp8>(h, j);
-      int av = a_val(blk, r, k);
-      if (s == 0 && j == 0 && lane == 0 && inject) av = av == 4 ? 3 : av + 1;
-      put<kFp8>(a, j, lowp_code<kFp8>(av));
-      put<kFp8>(b, j, lowp_code<kFp8>(b_val(blk, k, r)));
-    }
-    const int sa = 127 + scale_exp(1, r, 2 * s + h, 0);
-    const int sb = 127 + scale_exp(1, r, 2 * s + h, 1);
-    acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(a, b, acc, kFp8, kFp8, 0, sa, 0, sb);
-  }
-  uint32_t bad = 0;
-  for (int reg = 0; reg < 16; ++reg) {
-    const int row = cd_row32(reg, h);
-    int ref = 0;
-    for (int kb = 0; kb < 2 * ksteps; ++kb) {
-      int part = 0;
-      for (int j = 0; j < 32; ++j) part += a_val(blk, row, 32 * kb + j) * b_val(blk, 32 * kb + j, r);
-      ref += part << (scale_exp(1, row, kb, 0) + scale_exp(1, r, kb, 1));
-    }
-    bad += acc[reg] != static_cast<float>(ref);
-  }
-  return bad;
-}
-
+// ---- the valu check: wrong results this lane sees (the MFMA checks: form_check, mfma_forms.h) ----
 __device__ __forceinline__ uint32_t check_valu(int lane, const uint32_t* __restrict__ expect, bool inject) {
   valu_state s = valu_init(lane);
   if (inject && lane == 0) s.x ^= 1u;
@@ -167,8 +113,8 @@ __global__ void __launch_bounds__(256) site_probe(int ksteps, int inject_check, 
   const uint32_t key = gw | (seed << 14);
   const bool inject = static_cast<int>(gw) < inject_waves;
   uint32_t bad[kSiteChecks];
-  bad[0] = wave_total(check_mfma(key, lane, ksteps, inject && inject_check == 0));
-  bad[1] = wave_total(check_lowp(key, lane, ksteps, inject && inject_check == 1));
+  bad[0] = wave_total(form_check<FormBf16>(key, lane, ksteps, 0, inject && inject_check == 0));
+  bad[1] = wave_total(form_check<FormScaled<kFp8>>(key, lane, ksteps, 1, inject && inject_check == 1));
   bad[2] = wave_total(check_valu(lane, expect, inject && inject_check == 2));
   const uint32_t site_after = site_id();
   if (lane != 0) return;

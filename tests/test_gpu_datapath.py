@@ -112,3 +112,35 @@ def test_canary_run_covers_datapaths():
     assert r["ok"], r
     assert r["lowp_errors"] == 0 and r["lds_errors"] == 0 and r["lds_bytes"] >= 64 * 1024
     assert r["fp8_tflops"] > 0 and r["fp4_tflops"] > 0
+
+
+# ---- the smallest cases of the shared exactness check (ops/mfma_forms.h) -----------------
+FORMATS = ["fp8", "bf8", "fp4", "fp8_unscaled"]
+
+
+@pytest.mark.parametrize("vary", [False, True])
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_lowp_mfma_exact_at_one_step(fmt, vary):
+    """One k-step: the only step is both the first (the one an injection perturbs) and the last."""
+    from k8s_gpu_device_plugin_amd.ops import canary
+    assert canary.lowp_check(0, fmt, ksteps=1, vary_scale=vary) == 0
+
+
+@pytest.mark.parametrize("fmt", FORMATS)
+def test_one_injected_block_at_one_step_spoils_one_row(fmt):
+    """One perturbed element of A changes at most the 32 accumulators of its row."""
+    from k8s_gpu_device_plugin_amd.ops import canary
+    wrong = canary.lowp_check(0, fmt, ksteps=1, vary_scale=True, inject_blocks=1)
+    print("lowp_check %s, one step, one injected block: %d wrong" % (fmt, wrong))
+    assert 1 <= wrong <= 32
+
+
+@pytest.mark.parametrize("check", ["mfma", "lowp"])
+def test_site_probe_of_one_workgroup_locates_one_injected_wave(check):
+    """The site probe runs the same check bodies as the single-wave kernels."""
+    from k8s_gpu_device_plugin_amd.ops import canary
+    r = canary.site_probe(blocks=1, ksteps=1, inject=check, inject_waves=1)
+    print("site probe, one workgroup, inject %s: %d wrong at %s" % (check, r[check], r["bad_sites"]))
+    assert 1 <= r[check] <= 32
+    assert r["n_bad"] == 1 and len(r["bad_sites"]) == 1
+    assert [r[c] for c in ("mfma", "lowp", "valu") if c != check] == [0, 0]
