@@ -12,6 +12,9 @@ the repo snapshot to the GPU box):
   (in-kernel clock and rate per XCD, CU and SIMD), same ``hipcc`` line.
 * ``k8s_gpu_device_plugin_amd/ops/ldspath/libamdgpu_ldspath.so``  the canary's LDS-path check
   (LDS widths and atomics, lane swaps, the transposed read), same ``hipcc`` line.
+* ``k8s_gpu_device_plugin_amd/ops/matforms/libamdgpu_matforms.so``  the stand-alone matrix-forms
+  check (f16, i8, f32, f64, fp6, mixed MX and 16x16 MFMA), same ``hipcc`` line; not a row of
+  ``HIP_LIBS`` yet: ``build_matforms()`` or ``--matforms`` builds it.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -24,7 +27,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms]``
 """
 from __future__ import annotations
 
@@ -95,6 +98,12 @@ HOSTLINK_SOURCES, HOSTLINK_HEADERS, HOSTLINK_LIB = _HOSTLINK["sources"], _HOSTLI
 PACE_SOURCES, PACE_HEADERS, PACE_LIB = _PACE["sources"], _PACE["headers"], _PACE["lib"]
 LDSPATH_SOURCES, LDSPATH_HEADERS, LDSPATH_LIB = _LDSPATH["sources"], _LDSPATH["headers"], _LDSPATH["lib"]
 HOSTLINK_DIR, PACE_DIR, LDSPATH_DIR = (os.path.dirname(lib) for lib in (HOSTLINK_LIB, PACE_LIB, LDSPATH_LIB))
+
+# The matrix-forms check stands beside the table: canary.run() and the plugin do not call it yet,
+# so build_canaries(), build_all() and the default path of main() leave it alone.
+_MATFORMS = _hip_lib("matforms", "matforms", ("matforms.hip",), ("matforms.h", "matforms_host.h", "matforms_forms.h"))
+MATFORMS_SOURCES, MATFORMS_HEADERS, MATFORMS_LIB = _MATFORMS["sources"], _MATFORMS["headers"], _MATFORMS["lib"]
+MATFORMS_DIR = os.path.dirname(MATFORMS_LIB)
 
 
 def native_ext_path() -> str:
@@ -371,6 +380,10 @@ def build_ldspath(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_LDSPATH)
 
 
+def build_matforms(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_MATFORMS)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -395,7 +408,11 @@ def main(argv=None) -> int:
     ap.add_argument("--fuzz", nargs="*", choices=FUZZ_TARGETS, default=None,
                     help="build and run libFuzzer targets (all when none named)")
     ap.add_argument("--fuzz-seconds", type=float, default=30.0)
+    ap.add_argument("--matforms", action="store_true", help="build only the matrix-forms check's library")
     args = ap.parse_args(argv)
+    if args.matforms:
+        build_matforms(force=args.force)
+        return 0
     if args.fuzz is not None:
         rc = 0
         for t in args.fuzz or FUZZ_TARGETS:
