@@ -149,6 +149,15 @@ int partitions_of_mode(const std::string& mode) {
   return 0;
 }
 
+// bit of a memory partition mode in amdsmi's nps_cap_mask (NPS1 = bit 0 ... NPS8 = bit 3); 0 = unknown
+uint32_t nps_bit(const std::string& mode) {
+  if (mode == "NPS1") return 1;
+  if (mode == "NPS2") return 2;
+  if (mode == "NPS4") return 4;
+  if (mode == "NPS8") return 8;
+  return 0;
+}
+
 }  // namespace
 
 bool amdsmi_available(bool keep) {
@@ -402,14 +411,23 @@ class AmdSmiBackend : public Backend {
     std::memset(&prof, 0, sizeof(prof));
     uint32_t part_ids[AMDSMI_MAX_ACCELERATOR_PARTITIONS] = {};
     if (amdsmi_get_gpu_accelerator_partition_profile(h0, &prof, part_ids) == AMDSMI_STATUS_SUCCESS &&
-        prof.num_partitions > 0 && prof.num_partitions <= AMDSMI_MAX_ACCELERATOR_PARTITIONS &&
-        profile_type_name(prof.profile_type)[0] != '\0') {
-      g.partition_profile = profile_type_name(prof.profile_type);
-      g.profile_partitions = static_cast<int>(prof.num_partitions);
-      g.profile_index = static_cast<int>(prof.profile_index);
-      if (g.compute_partition.empty()) g.compute_partition = g.partition_profile;
-      if (g.nps_caps == 0) g.nps_caps = prof.memory_caps.nps_cap_mask & 0xF;
+        prof.num_partitions > 0 && prof.num_partitions <= AMDSMI_MAX_ACCELERATOR_PARTITIONS) {
+      // A guest's driver answers with the partition count alone (type INVALID, no index, no
+      // caps: it has no profile table to look the type up in); the type is then the mode
+      // amdsmi_get_gpu_compute_partition named, if that mode has this many partitions.
+      std::string type = profile_type_name(prof.profile_type);
+      if (type.empty() && partitions_of_mode(g.compute_partition) == static_cast<int>(prof.num_partitions))
+        type = g.compute_partition;
+      if (!type.empty()) {
+        g.partition_profile = type;
+        g.profile_partitions = static_cast<int>(prof.num_partitions);
+        g.profile_index = static_cast<int>(prof.profile_index);
+        if (g.compute_partition.empty()) g.compute_partition = g.partition_profile;
+        if (g.nps_caps == 0) g.nps_caps = prof.memory_caps.nps_cap_mask & 0xF;
+      }
     }
+    // no capability mask from either call: the memory mode the GPU runs in is one it supports
+    if (g.nps_caps == 0) g.nps_caps = nps_bit(g.memory_partition);
     // Every profile the GPU supports (the reference's mixed strategy asks NVML for every
     // MIG profile, resource/resources.go:43-51 VisitMigProfiles).
     // The list needs root (AMDSMI_STATUS_NO_PERM as an ordinary user on the MI355X box,

@@ -109,6 +109,9 @@ void HealthMonitor::emit_locked(HealthUpdate u) {
 }
 
 namespace {
+// how long an unchanged firmware-clock reading says nothing about the clock (on_sample)
+constexpr double kFwStepS = 1.5;
+
 std::pair<std::string, std::string> link_of(const std::string& a, const std::string& b) {
   return a < b ? std::make_pair(a, b) : std::make_pair(b, a);
 }
@@ -382,7 +385,11 @@ void HealthMonitor::on_sample(int gpu, bool ok, const GpuSample& s) {
           const double dt = now_b - st.fw_read_at, dc = s.fw_clock_s - st.fw_clock;
           // two readings closer than 20 ms say nothing about the rate: this one is skipped
           // and the next is compared with the previous one (never with an unjudged reading)
-          too_close = dt < 0.02;
+          // and so does a reading that has not moved for less than kFwStepS: a guest reads
+          // gpu_metrics through a host that refreshes it once a second, so its clock comes
+          // in steps; the rate is then judged from one step to the next (a frozen clock is
+          // one that stays put for longer)
+          too_close = dt < 0.02 || (dc == 0 && dt < kFwStepS);
           if (!too_close) {
             if (dc > 0 && dc / dt > 0.5 && dc / dt < 2.0) {
               ++st.fw_adv_n;

@@ -72,6 +72,12 @@ def test_partition_metrics_agree_with_the_socket_blob(be):
     idle = be.sample(0)
     print("idle: partition busy", idle.partition_gfx_busy_pct, "source", idle.partition_busy_source,
           "gfx", idle.gfx_activity_pct, "vram", idle.partition_vram_used_bytes, idle.vram_used_bytes)
+    # the partition tables are sysfs attributes of the driver's (xcp_metrics, per partition
+    # under xcp/); a guest's device directory has neither, and amdsmi has nothing to read
+    dev = "/sys/bus/pci/devices/%s" % gpus[0].bdf.lower()
+    if (idle.ok and idle.partition_busy_source[0] == 2 and not os.path.exists(dev + "/xcp_metrics")
+            and not os.path.isdir(dev + "/xcp")):
+        pytest.skip("the driver exposes no partition metrics table here (nothing under %s)" % dev)
     assert idle.ok and idle.partition_busy_source[0] == 1, idle.partition_busy_source
     if len(gpus[0].partitions) != 1:
         pytest.skip("the box is partitioned; the whole-GPU comparison needs SPX")
