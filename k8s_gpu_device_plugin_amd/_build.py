@@ -15,6 +15,9 @@ the repo snapshot to the GPU box):
 * ``k8s_gpu_device_plugin_amd/ops/matforms/libamdgpu_matforms.so``  the stand-alone matrix-forms
   check (f16, i8, f32, f64, fp6, mixed MX and 16x16 MFMA), same ``hipcc`` line; not a row of
   ``HIP_LIBS`` yet: ``build_matforms()`` or ``--matforms`` builds it.
+* ``k8s_gpu_device_plugin_amd/ops/valu/libamdgpu_valu.so``  the stand-alone vector-ALU check
+  (transcendentals, division chains, packed and dot-product math, bit operations, the fp8 / bf8 /
+  fp4 conversions), same ``hipcc`` line; beside ``HIP_LIBS`` likewise: ``build_valu()`` or ``--valu``.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -27,7 +30,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N] [--matforms]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu]``
 """
 from __future__ import annotations
 
@@ -104,6 +107,10 @@ HOSTLINK_DIR, PACE_DIR, LDSPATH_DIR = (os.path.dirname(lib) for lib in (HOSTLINK
 _MATFORMS = _hip_lib("matforms", "matforms", ("matforms.hip",), ("matforms.h", "matforms_host.h", "matforms_forms.h"))
 MATFORMS_SOURCES, MATFORMS_HEADERS, MATFORMS_LIB = _MATFORMS["sources"], _MATFORMS["headers"], _MATFORMS["lib"]
 MATFORMS_DIR = os.path.dirname(MATFORMS_LIB)
+# ... and so does the vector-ALU check.
+_VALU = _hip_lib("valu", "valu", ("valu.hip",), ("valu.h", "valu_host.h", "valu_ops.h"))
+VALU_SOURCES, VALU_HEADERS, VALU_LIB = _VALU["sources"], _VALU["headers"], _VALU["lib"]
+VALU_DIR = os.path.dirname(VALU_LIB)
 
 
 def native_ext_path() -> str:
@@ -384,6 +391,10 @@ def build_matforms(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_MATFORMS)
 
 
+def build_valu(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_VALU)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -409,9 +420,13 @@ def main(argv=None) -> int:
                     help="build and run libFuzzer targets (all when none named)")
     ap.add_argument("--fuzz-seconds", type=float, default=30.0)
     ap.add_argument("--matforms", action="store_true", help="build only the matrix-forms check's library")
+    ap.add_argument("--valu", action="store_true", help="build only the vector-ALU check's library")
     args = ap.parse_args(argv)
-    if args.matforms:
-        build_matforms(force=args.force)
+    if args.matforms or args.valu:
+        if args.matforms:
+            build_matforms(force=args.force)
+        if args.valu:
+            build_valu(force=args.force)
         return 0
     if args.fuzz is not None:
         rc = 0
