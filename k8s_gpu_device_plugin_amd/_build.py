@@ -18,6 +18,9 @@ the repo snapshot to the GPU box):
 * ``k8s_gpu_device_plugin_amd/ops/valu/libamdgpu_valu.so``  the stand-alone vector-ALU check
   (transcendentals, division chains, packed and dot-product math, bit operations, the fp8 / bf8 /
   fp4 conversions), same ``hipcc`` line; beside ``HIP_LIBS`` likewise: ``build_valu()`` or ``--valu``.
+* ``k8s_gpu_device_plugin_amd/ops/mxgemm/libamdgpu_mxgemm.so``  the stand-alone block-scaled
+  matrix-path check (an LDS-staged MX-fp8 / bf8 / fp4 GEMM with ABFT checksums), same ``hipcc`` line;
+  beside ``HIP_LIBS`` likewise: ``build_mxgemm()`` or ``--mxgemm``.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -30,7 +33,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm]``
 """
 from __future__ import annotations
 
@@ -111,6 +114,10 @@ MATFORMS_DIR = os.path.dirname(MATFORMS_LIB)
 _VALU = _hip_lib("valu", "valu", ("valu.hip",), ("valu.h", "valu_host.h", "valu_ops.h"))
 VALU_SOURCES, VALU_HEADERS, VALU_LIB = _VALU["sources"], _VALU["headers"], _VALU["lib"]
 VALU_DIR = os.path.dirname(VALU_LIB)
+# ... and the block-scaled matrix-path check.
+_MXGEMM = _hip_lib("mxgemm", "mxgemm", ("mxgemm.hip",), ("mxgemm.h", "mxgemm_host.h"))
+MXGEMM_SOURCES, MXGEMM_HEADERS, MXGEMM_LIB = _MXGEMM["sources"], _MXGEMM["headers"], _MXGEMM["lib"]
+MXGEMM_DIR = os.path.dirname(MXGEMM_LIB)
 
 
 def native_ext_path() -> str:
@@ -395,6 +402,10 @@ def build_valu(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_VALU)
 
 
+def build_mxgemm(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_MXGEMM)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -421,12 +432,15 @@ def main(argv=None) -> int:
     ap.add_argument("--fuzz-seconds", type=float, default=30.0)
     ap.add_argument("--matforms", action="store_true", help="build only the matrix-forms check's library")
     ap.add_argument("--valu", action="store_true", help="build only the vector-ALU check's library")
+    ap.add_argument("--mxgemm", action="store_true", help="build only the block-scaled matrix-path check's library")
     args = ap.parse_args(argv)
-    if args.matforms or args.valu:
+    if args.matforms or args.valu or args.mxgemm:
         if args.matforms:
             build_matforms(force=args.force)
         if args.valu:
             build_valu(force=args.force)
+        if args.mxgemm:
+            build_mxgemm(force=args.force)
         return 0
     if args.fuzz is not None:
         rc = 0
