@@ -21,6 +21,9 @@ the repo snapshot to the GPU box):
 * ``k8s_gpu_device_plugin_amd/ops/mxgemm/libamdgpu_mxgemm.so``  the stand-alone block-scaled
   matrix-path check (an LDS-staged MX-fp8 / bf8 / fp4 GEMM with ABFT checksums), same ``hipcc`` line;
   beside ``HIP_LIBS`` likewise: ``build_mxgemm()`` or ``--mxgemm``.
+* ``k8s_gpu_device_plugin_amd/ops/attn/libamdgpu_attn.so``  the stand-alone attention-path check
+  (a fused bf16 flash-attention forward with exact and bounded verdicts), same ``hipcc`` line;
+  beside ``HIP_LIBS`` likewise: ``build_attn()`` or ``--attn``.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -33,7 +36,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm] [--attn]``
 """
 from __future__ import annotations
 
@@ -118,6 +121,10 @@ VALU_DIR = os.path.dirname(VALU_LIB)
 _MXGEMM = _hip_lib("mxgemm", "mxgemm", ("mxgemm.hip",), ("mxgemm.h", "mxgemm_host.h"))
 MXGEMM_SOURCES, MXGEMM_HEADERS, MXGEMM_LIB = _MXGEMM["sources"], _MXGEMM["headers"], _MXGEMM["lib"]
 MXGEMM_DIR = os.path.dirname(MXGEMM_LIB)
+# ... and the attention-path check.
+_ATTN = _hip_lib("attn", "attn", ("attn.hip",), ("attn.h", "attn_host.h"))
+ATTN_SOURCES, ATTN_HEADERS, ATTN_LIB = _ATTN["sources"], _ATTN["headers"], _ATTN["lib"]
+ATTN_DIR = os.path.dirname(ATTN_LIB)
 
 
 def native_ext_path() -> str:
@@ -406,6 +413,10 @@ def build_mxgemm(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_MXGEMM)
 
 
+def build_attn(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_ATTN)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -433,14 +444,17 @@ def main(argv=None) -> int:
     ap.add_argument("--matforms", action="store_true", help="build only the matrix-forms check's library")
     ap.add_argument("--valu", action="store_true", help="build only the vector-ALU check's library")
     ap.add_argument("--mxgemm", action="store_true", help="build only the block-scaled matrix-path check's library")
+    ap.add_argument("--attn", action="store_true", help="build only the attention-path check's library")
     args = ap.parse_args(argv)
-    if args.matforms or args.valu or args.mxgemm:
+    if args.matforms or args.valu or args.mxgemm or args.attn:
         if args.matforms:
             build_matforms(force=args.force)
         if args.valu:
             build_valu(force=args.force)
         if args.mxgemm:
             build_mxgemm(force=args.force)
+        if args.attn:
+            build_attn(force=args.force)
         return 0
     if args.fuzz is not None:
         rc = 0
