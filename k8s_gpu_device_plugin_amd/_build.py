@@ -24,6 +24,9 @@ the repo snapshot to the GPU box):
 * ``k8s_gpu_device_plugin_amd/ops/attn/libamdgpu_attn.so``  the stand-alone attention-path check
   (a fused bf16 flash-attention forward with exact and bounded verdicts), same ``hipcc`` line;
   beside ``HIP_LIBS`` likewise: ``build_attn()`` or ``--attn``.
+* ``k8s_gpu_device_plugin_amd/ops/decode/libamdgpu_decode.so``  the stand-alone decode-attention check
+  (paged KV cache, GQA, split-KV with a two-level log-sum-exp merge), same ``hipcc`` line;
+  beside ``HIP_LIBS`` likewise: ``build_decode()`` or ``--decode``.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -36,7 +39,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm] [--attn]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm] [--attn] [--decode]``
 """
 from __future__ import annotations
 
@@ -125,6 +128,10 @@ MXGEMM_DIR = os.path.dirname(MXGEMM_LIB)
 _ATTN = _hip_lib("attn", "attn", ("attn.hip",), ("attn.h", "attn_host.h"))
 ATTN_SOURCES, ATTN_HEADERS, ATTN_LIB = _ATTN["sources"], _ATTN["headers"], _ATTN["lib"]
 ATTN_DIR = os.path.dirname(ATTN_LIB)
+# ... and the decode-attention check.
+_DECODE = _hip_lib("decode", "decode", ("decode.hip",), ("decode.h", "decode_host.h"))
+DECODE_SOURCES, DECODE_HEADERS, DECODE_LIB = _DECODE["sources"], _DECODE["headers"], _DECODE["lib"]
+DECODE_DIR = os.path.dirname(DECODE_LIB)
 
 
 def native_ext_path() -> str:
@@ -417,6 +424,10 @@ def build_attn(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_ATTN)
 
 
+def build_decode(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_DECODE)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -445,8 +456,9 @@ def main(argv=None) -> int:
     ap.add_argument("--valu", action="store_true", help="build only the vector-ALU check's library")
     ap.add_argument("--mxgemm", action="store_true", help="build only the block-scaled matrix-path check's library")
     ap.add_argument("--attn", action="store_true", help="build only the attention-path check's library")
+    ap.add_argument("--decode", action="store_true", help="build only the decode-attention check's library")
     args = ap.parse_args(argv)
-    if args.matforms or args.valu or args.mxgemm or args.attn:
+    if args.matforms or args.valu or args.mxgemm or args.attn or args.decode:
         if args.matforms:
             build_matforms(force=args.force)
         if args.valu:
@@ -455,6 +467,8 @@ def main(argv=None) -> int:
             build_mxgemm(force=args.force)
         if args.attn:
             build_attn(force=args.force)
+        if args.decode:
+            build_decode(force=args.force)
         return 0
     if args.fuzz is not None:
         rc = 0
