@@ -27,6 +27,10 @@ the repo snapshot to the GPU box):
 * ``k8s_gpu_device_plugin_amd/ops/decode/libamdgpu_decode.so``  the stand-alone decode-attention check
   (paged KV cache, GQA, split-KV with a two-level log-sum-exp merge), same ``hipcc`` line;
   beside ``HIP_LIBS`` likewise: ``build_decode()`` or ``--decode``.
+* ``k8s_gpu_device_plugin_amd/ops/decode8/libamdgpu_decode8.so``  the stand-alone fp8 decode-attention check
+  (the same path on a paged e4m3 KV cache with per-KV-head scales: 2 KiB pages, 128 B rows through LDS,
+  fp8 decoded to bf16 in registers, the 8-bit transposed LDS read), same ``hipcc`` line; beside ``HIP_LIBS``
+  likewise: ``build_decode8()`` or ``--decode8``.
 * ``k8s_gpu_device_plugin_amd/_native_bench*.so``  the load generators and latency
   probes of ``bench.py``, ``scripts/`` and the tests (``tests/native/loadgen.cpp``,
   ``tests/native/bench_bindings.cpp``) over the same core objects.  Harness only: the
@@ -39,7 +43,7 @@ the repo snapshot to the GPU box):
   (HTTP/1.1 ops server).
 
 Usage: ``python -m k8s_gpu_device_plugin_amd._build [--force] [--sanitize address|thread]
-[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm] [--attn] [--decode]``
+[--fuzz TARGET... --fuzz-seconds N] [--matforms] [--valu] [--mxgemm] [--attn] [--decode] [--decode8]``
 """
 from __future__ import annotations
 
@@ -132,6 +136,10 @@ ATTN_DIR = os.path.dirname(ATTN_LIB)
 _DECODE = _hip_lib("decode", "decode", ("decode.hip",), ("decode.h", "decode_host.h"))
 DECODE_SOURCES, DECODE_HEADERS, DECODE_LIB = _DECODE["sources"], _DECODE["headers"], _DECODE["lib"]
 DECODE_DIR = os.path.dirname(DECODE_LIB)
+# ... and the fp8 decode-attention check, which reads decode's host header for all that is not fp8.
+_DECODE8 = _hip_lib("decode8", "decode8", ("decode8.hip",), ("decode8.h", "decode8_host.h", "../decode/decode_host.h"))
+DECODE8_SOURCES, DECODE8_HEADERS, DECODE8_LIB = _DECODE8["sources"], _DECODE8["headers"], _DECODE8["lib"]
+DECODE8_DIR = os.path.dirname(DECODE8_LIB)
 
 
 def native_ext_path() -> str:
@@ -428,6 +436,10 @@ def build_decode(force: bool = False, verbose: bool = True) -> str:
     return _build_hip_lib(force=force, verbose=verbose, **_DECODE)
 
 
+def build_decode8(force: bool = False, verbose: bool = True) -> str:
+    return _build_hip_lib(force=force, verbose=verbose, **_DECODE8)
+
+
 def build_canaries(force: bool = False) -> None:
     """Every library of ``HIP_LIBS``."""
     for row in HIP_LIBS:
@@ -457,8 +469,9 @@ def main(argv=None) -> int:
     ap.add_argument("--mxgemm", action="store_true", help="build only the block-scaled matrix-path check's library")
     ap.add_argument("--attn", action="store_true", help="build only the attention-path check's library")
     ap.add_argument("--decode", action="store_true", help="build only the decode-attention check's library")
+    ap.add_argument("--decode8", action="store_true", help="build only the fp8 decode-attention check's library")
     args = ap.parse_args(argv)
-    if args.matforms or args.valu or args.mxgemm or args.attn or args.decode:
+    if args.matforms or args.valu or args.mxgemm or args.attn or args.decode or args.decode8:
         if args.matforms:
             build_matforms(force=args.force)
         if args.valu:
@@ -469,6 +482,8 @@ def main(argv=None) -> int:
             build_attn(force=args.force)
         if args.decode:
             build_decode(force=args.force)
+        if args.decode8:
+            build_decode8(force=args.force)
         return 0
     if args.fuzz is not None:
         rc = 0
